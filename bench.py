@@ -22,7 +22,20 @@ bracketed by barrier + device synchronize on both sides with the inputs resident
 in HBM; the reported time is the sum over the K timed steps (MAX over ranks).
 The synthetic scene is stationary (landmarks re-spawn in the frustum, gfpl_synth
 `respawn`), so per-step work does not drift with --steps; the bench line carries
-the per-step mean feature counts.  `host_fed` is measured after the timed steps:
+the per-step mean feature counts.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps,
+writes its outputs when `--dump-outputs DIR` is given and prints the result line.
+Its inputs are 512 distinct generated sequences per frame, uploaded once and copied
+on the device into the rest of the batch (sequence b tracks generator sequence
+b % 512 from its own state), so the host generator does not dominate the run.
+`--dump-outputs DIR` writes what the last timed step computed (pose, features and
+matched lists of a fixed seeded sample of the sequences, every sequence's step
+record) as DIR/<name>.npy; the same arguments give the same inputs and outputs.
+Everything below is measured or checked only with `--full`, which also generates
+every sequence's own input frames (with >= 8 generator threads).
+
+`host_fed` is measured after the timed steps:
 two frames held in pinned host memory are uploaded on the copy stream into the
 two staging buffers while the step on the other one runs (PCIe-inclusive rate).
 
@@ -98,13 +111,23 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=65536, help="sequences per GPU (reduced only if HBM is short)")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every further leg (sampled parity against the CPU oracle, "
+                         "proven leg, host-fed rate, B = 1 latency, CPU baseline, detection and images-to-poses "
+                         "rates; each has its own --no-* switch) and generate every sequence's own input frames; "
+                         "without it the run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64): the frame "
+                         "state, pose and matched lists of a fixed seeded sample of the sequences and every "
+                         "sequence's step record")
     ap.add_argument("--no-detect", action="store_true", help="skip the ORB / LBD detection rates")
     ap.add_argument("--gen-threads", type=int, default=16,
                     help="host threads generating the input frames (capped by this rank's share of the cores)")
     ap.add_argument("--distinct", type=int, default=0,
-                    help="distinct synthetic sequences per rank: 0 = all B with >= 8 generator threads, else one chunk's "
-                         "worth (8 ranks sharing a host; each uploaded to every chunk of the batch) — a fixed rule "
-                         "of (B, threads), never a timing, so one command always tracks the same inputs")
+                    help="distinct synthetic sequences per rank: 0 = with --full all B with >= 8 generator threads, "
+                         "else one chunk's worth (8 ranks sharing a host), and 512 without --full (uploaded once, "
+                         "copied on the device into the rest of the batch) — a fixed rule of (--full, B, threads), "
+                         "never a timing, so one command always tracks the same inputs")
     ap.add_argument("--chunk", type=int, default=0,
                     help="sequences per pinned host chunk of the input ring (0: B/8 within [256, 2048])")
     ap.add_argument("--no-host-fed", action="store_true", help="skip the pipelined host-fed (PCIe) measurement")
@@ -471,6 +494,80 @@ def latency_b1(ctx, cam, cfg, sp, kp_cap, kl_cap, seq, warmup, steps):
                       f"CPU: oracle/ C++ on one host thread, the same frames"}
 
 
+# ------------------------------------------------- replicated inputs, outputs --
+PLAIN_DISTINCT = 512     # distinct generated sequences per rank of a run without --full
+FRAME_FIELDS = ["n_kp_l", "n_kp_r", "kp_l", "kp_r", "pdesc_l", "pdesc_r", "n_kl_l", "n_kl_r",
+                "kl_l", "kl_r", "ldesc_l", "ldesc_r", "pyr_r", "time_stamp"]   # gfpl.HostBatch.arrays() order
+
+
+class _DevBytes:
+    """n bytes of device memory at ptr, for torch.as_tensor (no copy, not owned)."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "|u1", "data": (int(ptr), False),
+                                         "strides": None, "version": 2}
+
+
+def replicate_staged(dv, B, n, row_bytes, dev):
+    """Copy sequences [0, n) of every field of the staged device frames dv ([B][...] row-major,
+    row_bytes per sequence) into sequences [n, B), on the current stream (the context's)."""
+    import torch
+    for name, rb in zip(FRAME_FIELDS, row_bytes):
+        t = torch.as_tensor(_DevBytes(getattr(dv, name), B * rb), device=dev).view(B, rb)
+        for s0 in range(n, B, n):
+            m = min(n, B - s0)
+            t[s0:s0 + m].copy_(t[:m])
+
+
+DUMP_SEQS = 256          # --dump-outputs: sampled sequences (pose, counts, track counters)
+DUMP_FEATURE_SEQS = 32   # the first of them with their feature arrays and matched lists (at kp_cap 2048)
+DUMP_PT = ["pt_pl", "pt_disp", "pt_P", "pt_sigma2", "pt_idx", "pt_level", "pdesc"]
+DUMP_LS = ["ls_spl", "ls_epl", "ls_sdisp", "ls_edisp", "ls_angle", "ls_sigma2", "ls_sP", "ls_eP",
+           "ls_le", "ls_idx", "ls_level", "ldesc"]
+DUMP_POSE = ["Tfw", "DT", "DT_cov", "Tfw_cov", "DT_cov_eig"]
+DUMP_TRACK = ["n_inliers", "n_inliers_pt", "n_inliers_ls", "num_frame_loss"]
+
+
+def dump_outputs(path, h, B, kp_cap, kl_cap):
+    """What the last step left for its caller, as path/<name>.npy (float64; descriptors float32):
+    of a fixed seeded sample of the sequences the new frame's pose, feature counts and the track
+    counters (gfpl_read_frame, gfpl_read_last_track); of the first of these also the new frame's
+    stereo features (the fields defined at this point, rows past the count zeroed) and the matched
+    lists (padded with -1); and every sequence's step record (gfpl_debug_step_records)."""
+    import gfpl
+    os.makedirs(path, exist_ok=True)
+    seqs = np.random.default_rng(0x5EED).permutation(B)[:DUMP_SEQS]
+    n_feat = min(len(seqs), max(1, DUMP_FEATURE_SEQS * 2048 // kp_cap))
+    out = {"seq": seqs.astype(np.float64)}
+    cols = {n: [] for n in DUMP_POSE + ["err_norm", "n_pt", "n_ls", "n_matched_pt", "n_matched_ls"] + DUMP_TRACK}
+    feat = {n: [] for n in DUMP_PT + DUMP_LS + ["matched_pt", "matched_ls"]}
+    for i, b in enumerate(int(x) for x in seqs):
+        fh, tr = h.read_frame(gfpl.PREV, b), h.read_last_track(b)   # PREV after the update: the new frame
+        for n in DUMP_POSE:
+            cols[n].append(fh.get(n))
+        for n, v in (("err_norm", fh.s.err_norm), ("n_pt", fh.n_pt), ("n_ls", fh.n_ls),
+                     ("n_matched_pt", len(tr["matched_pt"])), ("n_matched_ls", len(tr["matched_ls"]))):
+            cols[n].append(v)
+        for n in DUMP_TRACK:
+            cols[n].append(tr[n])
+        if i >= n_feat:
+            continue
+        for n in DUMP_PT + DUMP_LS:
+            a = fh.arr[n].astype(np.float32 if n in ("pdesc", "ldesc") else np.float64)
+            a[(fh.n_pt if n in DUMP_PT else fh.n_ls):] = 0
+            feat[n].append(a)
+        for n, cap in (("matched_pt", gfpl.MAX_MATCHED_PT), ("matched_ls", gfpl.MAX_MATCHED_LS)):
+            a = np.full(cap, -1.0)
+            a[:len(tr[n])] = tr[n]
+            feat[n].append(a)
+    out.update({n: np.asarray(v, dtype=np.float64) for n, v in cols.items()})
+    out.update({n: np.stack(v) for n, v in feat.items()})
+    rec = h.debug_step_records()
+    out["step_records"] = (rec if rec.nbytes <= (16 << 20) else rec[np.sort(seqs)]).astype(np.float64)
+    for n, a in out.items():
+        np.save(os.path.join(path, n + ".npy"), a)
+
+
 # ----------------------------------------------------------------------- main --
 def detection_rates(cam, upload_Bps, n_img=256, n_lines=300, steps=5):
     """SURVEY §8(f)1-2 on the bench camera, measured after the timed tracking steps (not part of
@@ -694,8 +791,10 @@ def main():
     B, W, K = args.batch, args.warmup, args.steps
     KP, KL = (8192, 2048) if args.workload == "cfg5" else (2048, 512)
     keep = []
-    # init + warmup + timed + the proven leg's (one untimed + --proven-steps) + the two host-fed frames
-    n_frames_needed = W + K + 3 + (args.proven_steps + 1 if args.proven_steps > 0 else 0)
+    # init + warmup + timed; --full: + the proven leg's (one untimed + --proven-steps) + the two host-fed frames
+    n_frames_needed = W + K + 1
+    if args.full:
+        n_frames_needed += 2 + (args.proven_steps + 1 if args.proven_steps > 0 else 0)
     if args.workload == "cfg4":
         if n_frames_needed > gfpl.EUROC_MAX_POSES:
             print(f"error: cfg4 needs {n_frames_needed} ground-truth poses, {gfpl.EUROC_MAX_POSES} stored",
@@ -736,53 +835,66 @@ def main():
     gen_threads = max(1, min(args.gen_threads, share))
     chunk = args.chunk or min(2048, max(256, (B // 8 + 63) // 64 * 64))   # (<= 4.2 GB pinned per rank)
     chunk = min(chunk, B)
-    ring = [gfpl.HostBatch(cam, sp_up, chunk, KP, KL, seq0=seq0, pinned=not dry) for _ in range(2)]
-    pinned_bytes = 0 if dry else sum(r.nbytes() for r in ring)
-    t_gen = 0.0
-    # input generation per rank: the generator costs ~1 ms per sequence-frame and core, the
-    # GPU step ~2 us per sequence-frame, so overlapping the two gains < 3%; with several ranks
-    # sharing one host's cores (8 ranks: 2 cores each) one chunk of distinct sequences is
-    # generated per frame and uploaded into every chunk of the batch — every sequence is still
-    # tracked on the GPU from its own state.  The rule depends on (B, threads) only: a timing-based
-    # choice once gave two runs of one command different inputs (round-5 review, item 1); the
-    # thread count is this rank's share of the host's cores (cgroup quota / ranks per node)
-    n_proven = args.proven_steps + 1 if (world == 1 and args.proven_steps > 0 and not dry and
-                                         int(cfg.cut_proof) == 0) else 0
-    n_frames_gen = W + K + 1 + n_proven + (0 if (world > 1 or args.no_host_fed or dry) else 2)
-    probe_n = min(chunk, 128)
-    t0 = time.perf_counter()
-    ring[1].fill(0, gen_threads, seq0=seq0, n=probe_n)
-    per_seq_frame = (time.perf_counter() - t0) / probe_n
-    gen_full_s = per_seq_frame * B * n_frames_gen
     if args.distinct > 0:
         distinct = min(args.distinct, B)
+    elif not args.full:
+        distinct = min(PLAIN_DISTINCT, B)
     else:
         distinct = B if gen_threads >= 8 else chunk   # 8 ranks on one 16-core share: 2 threads each
     if distinct < B:
-        distinct = min(distinct, chunk)   # generated into one ring chunk, tiled, uploaded chunk-wise
-    gen_projected_s = per_seq_frame * distinct * n_frames_gen
+        distinct = min(distinct, chunk)   # generated into one ring chunk, uploaded once, replicated on the device
     replicate = distinct < B
+    ring_rows = distinct if replicate else chunk
+    ring = [gfpl.HostBatch(cam, sp_up, ring_rows, KP, KL, seq0=seq0, pinned=not dry) for _ in range(2)]
+    pinned_bytes = 0 if dry else sum(r.nbytes() for r in ring)
+    row_bytes = [a.nbytes // a.shape[0] for a in ring[0].arrays()]   # per sequence, in gfpl_frames field order
+    t_gen = 0.0
+    # input generation per rank: the generator costs ~1 ms per sequence-frame and core, the
+    # GPU step ~2 us per sequence-frame, so overlapping the two gains < 3%; with several ranks
+    # sharing one host's cores (8 ranks: 2 cores each), and in every run without --full (whose
+    # time outside the steps is the generator's), `distinct` sequences are generated per frame,
+    # uploaded once and copied on the device into the rest of the batch — every sequence is still
+    # tracked on the GPU from its own state.  The rule (above) depends on (--full, B, threads) only: a
+    # timing-based choice once gave two runs of one command different inputs (round-5 review, item 1);
+    # the thread count is this rank's share of the host's cores (cgroup quota / ranks per node)
+    n_proven = args.proven_steps + 1 if (args.full and world == 1 and args.proven_steps > 0 and not dry and
+                                         int(cfg.cut_proof) == 0) else 0
+    host_fed_on = args.full and world == 1 and not args.no_host_fed and not dry
+    n_frames_gen = W + K + 1 + n_proven + (2 if host_fed_on else 0)
+    probe_n = min(ring_rows, 128)
+    probe_s = []
+    for _ in range(3):   # the fastest of three: the first touches the probe's pages, any may be preempted
+        t0 = time.perf_counter()
+        ring[1].fill(0, gen_threads, seq0=seq0, n=probe_n)
+        probe_s.append(time.perf_counter() - t0)
+    per_seq_frame = min(probe_s) / probe_n
+    gen_full_s = per_seq_frame * B * n_frames_gen
+    gen_projected_s = per_seq_frame * distinct * n_frames_gen
 
     h = None if dry else gfpl.StereoFrameHandler(ctx, B, KP, KL)
 
     def stage_frame(k, slot=0):
         """Generate frame k of this rank's B sequences chunk by chunk into the pinned ring and
         copy each chunk into staging buffer `slot` (gfpl_upload_frames_async); the next chunk
-        is generated while the previous one is copied.  Returns the staged device view."""
-        tick = []
+        is generated while the previous one is copied.  With fewer distinct sequences than B
+        the distinct ones are generated and uploaded into sequences [0, distinct) and copied
+        from there into the rest of the staging buffer on the device (sequence b tracks
+        generator sequence b % distinct).  Returns the staged device view."""
         if replicate:
             ring[0].fill(k, gen_threads, seq0=seq0, n=distinct)
-            for d0 in range(distinct, chunk, distinct):   # tile the distinct rows over the chunk
-                dn = min(distinct, chunk - d0)
-                for a in ring[0].arrays():
-                    a[d0:d0 + dn] = a[:dn]
+            if h is None:
+                return None
+            h.upload_wait(h.upload_async(ring[0].frames(distinct), 0, slot, l0_stride=int(cam.pyr_bytes)))
+            dv = h.staged_frames(slot)
+            replicate_staged(dv, B, distinct, row_bytes, dev)
+            return dv
+        tick = []
         for ci, s0 in enumerate(range(0, B, chunk)):
             n = min(chunk, B - s0)
-            hb = ring[0] if replicate else ring[ci % 2]
-            if ci >= 2 and h is not None and not replicate:
+            hb = ring[ci % 2]
+            if ci >= 2 and h is not None:
                 h.upload_wait(tick[ci - 2])   # the chunk's host buffer is free again
-            if not replicate:
-                hb.fill(k, gen_threads, seq0=seq0 + s0, n=n)
+            hb.fill(k, gen_threads, seq0=seq0 + s0, n=n)
             if h is not None:
                 tick.append(h.upload_async(hb.frames(n), s0, slot, l0_stride=int(cam.pyr_bytes)))
         if h is None:
@@ -816,10 +928,10 @@ def main():
         return
 
     sampler = None
-    if args.parity_seqs != 0:
+    if args.full and args.parity_seqs != 0:
         seqs = list(range(B)) if args.parity_seqs < 0 else [int(x) for x in np.linspace(0, B - 1, min(args.parity_seqs, B))]
         sampler = ParitySampler(cam, cfg, sp, KP, KL, seq0, seqs, share,
-                                seq_of=(lambda b: (b % chunk) % distinct) if replicate else None)
+                                seq_of=(lambda b: b % distinct) if replicate else None)
 
     def sync_all():
         torch.cuda.synchronize(dev)
@@ -860,6 +972,8 @@ def main():
         if rank == 0:   # progress (stderr): long runs under a watchdog keep writing
             print(f"[bench] step {k}/{W + K}: {1e3 * (ts1 - ts0):.2f} ms", file=sys.stderr, flush=True)
     elapsed = float(np.sum(step_s))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, h, B, KP, KL)   # before any further leg steps the sequences on
     if args.dump_records and rank == 0:
         np.save(args.dump_records, h.debug_step_records())
         try:
@@ -904,7 +1018,7 @@ def main():
                           f"{W + K + 2}..{W + K + n_proven}): the measured-mode line's decisions proven after the "
                           "fact, unproven sequences redone by the eager-proven search (DESIGN.md §3)"}
     host_fed = None
-    if world == 1 and not args.no_host_fed:
+    if host_fed_on:
         host_fed = host_fed_rate(h, cam, sp_up, B, KP, KL, seq0, W + K + 1 + n_proven, gen_threads, per_up, dev,
                                  distinct=distinct if replicate else B)
 
@@ -934,13 +1048,13 @@ def main():
                          "valu_insts_per_launch": pmc["SQ_INSTS_VALU"], "waves_per_launch": pmc.get("SQ_WAVES"),
                          "source": os.path.relpath(args.pmc, ROOT)}
         b1 = None
-        if world == 1 and not args.no_b1:
+        if args.full and world == 1 and not args.no_b1:
             try:
                 b1 = latency_b1(ctx, cam, cfg, sp, KP, KL, seq0, W, args.b1_steps)
             except Exception as e:   # reported, never fatal to the contract line
                 b1 = {"error": f"{type(e).__name__}: {e}"}
         cpu = None
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             nt = args.cpu_threads or cores
             cpu = cpu_baseline(cam, cfg, sp, KP, KL, nt, args.cpu_seconds, cores_info, gen_threads, W + K)
             if args.cpu_sweep_seconds > 0:
@@ -948,7 +1062,7 @@ def main():
                                                        gen_threads, W + K, cpu,
                                                        b1.get("cpu_1thread_ms_per_frame") if b1 else None)
         det = None
-        if world == 1 and not args.no_detect:
+        if args.full and world == 1 and not args.no_detect:
             up_Bps = host_fed["upload_GBps"] * 1e9 if host_fed and host_fed.get("upload_GBps") else 0.0
             det = detection_rates(cam, up_Bps)
             try:
@@ -978,8 +1092,9 @@ def main():
             "data": "synthetic (deterministic splitmix64 stereo detections + right ORB pyramid, gfpl_synth; "
                     "stationary scene: landmarks re-spawn in the frustum), generated per step on the host and "
                     "uploaded to HBM before each timed step" +
-                    (f"; {distinct} distinct generated sequences per rank, each uploaded to {B // distinct} of "
+                    (f"; {distinct} distinct generated sequences per rank, each the input of {B // distinct} of "
                      f"the {B} tracked sequences (host generation budget)" if replicate else ""),
+            "full": bool(args.full),
             "config": {"workload": desc, "sequences_per_gpu": B, "kp_per_side": int(sp.n_kp),
                        "kl_per_side": int(sp.n_kl), "gn_iters": "10+10",
                        "parallelism": f"sequences sharded 1/{world} per GPU",

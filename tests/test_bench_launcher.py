@@ -55,7 +55,7 @@ def test_eight_rank_generation_fits_its_budget():
     sequences, 20 + 5 steps): generating every sequence's frames would take minutes, so the
     rank generates one chunk of distinct sequences per frame and uploads it into every chunk
     (stated in the line), and its projected generation time stays within two minutes."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--batch", "16384",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--full", "--batch", "16384",
                         "--steps", "20", "--warmup", "5", "--no-cpu", "--gen-threads", "2"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -86,7 +86,7 @@ def test_cfg4_trajectory_covers_the_proven_leg():
     """cfg4's ground-truth trajectory must hold every frame the run generates, the proven leg's
     (one untimed + --proven-steps) included: 505 timed steps + init + 2 host-fed frames fit the 512
     stored poses only without the leg (a run that passed the check once failed at its first proven step)."""
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--workload", "cfg4", "--steps", "505",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--full", "--workload", "cfg4", "--steps", "505",
             "--warmup", "0", "--batch", "4", "--no-cpu", "--gen-threads", "1"]
     r = subprocess.run(base, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 2 and "ground-truth poses" in r.stderr

@@ -1,4 +1,5 @@
 export GFPL_LIB_DIR=${LIBV:-build/cutprof}
-mkdir -p gpurun_out
-timeout -k 10 300 python bench.py --batch 16384 --steps 1 --warmup 0 --no-cpu > gpurun_out/cutprof.log 2>&1; rc=$?
-grep -E "cutprof|cutstats|spprof" gpurun_out/cutprof.log | tail -24; exit $rc
+OUT=${OUT:-bench_out}   # output directory
+mkdir -p $OUT
+timeout -k 10 300 python bench.py --full --batch 16384 --steps 1 --warmup 0 --no-cpu > $OUT/cutprof.log 2>&1; rc=$?
+grep -E "cutprof|cutstats|spprof" $OUT/cutprof.log | tail -24; exit $rc

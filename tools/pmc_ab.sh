@@ -11,7 +11,7 @@ for v in "$@"; do
   rm -rf $OUT && mkdir -p $OUT
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c -d $OUT/$c -o $c -f csv -- \
-        python3 bench.py --batch $B --steps 2 --warmup 1 --no-cpu > $OUT/$c.log 2>&1 || { echo "$tag $c failed"; tail -5 $OUT/$c.log; exit 1; }
+        python3 bench.py --full --batch $B --steps 2 --warmup 1 --no-cpu > $OUT/$c.log 2>&1 || { echo "$tag $c failed"; tail -5 $OUT/$c.log; exit 1; }
   done
   echo "== $tag"
   python3 tools/pmc_summary.py $OUT $B $OUT/pmc.json | grep -E "k_stereo|k_pose|k_cut_search|k_cross" || true

@@ -12,7 +12,7 @@ i=0
 for P in "$P1" "$P2"; do
   i=$((i+1))
   timeout -k 10 400 rocprofv3 --kernel-trace --pmc $P -d $OUT/p$i -o p$i -f csv -- \
-      python3 bench.py --batch $B --steps 2 --warmup 1 --no-cpu > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $OUT/p$i.log; exit 1; }
+      python3 bench.py --full --batch $B --steps 2 --warmup 1 --no-cpu > $OUT/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $OUT/p$i.log; exit 1; }
 done
 python3 tools/pmc_summary.py $OUT $B $OUT/sq.json > /dev/null && python3 - "$OUT/sq.json" <<'PY'
 import json, sys

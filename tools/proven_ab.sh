@@ -8,7 +8,7 @@ O=gpurun_out/$1; shift; mkdir -p $O
 for d in "$@"; do
   tag=$(basename $d)
   if [ "$d" = default ]; then unset GFPL_LIB_DIR; else export GFPL_LIB_DIR=$(realpath $d); fi
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_$tag -o prof -f csv -- python3 bench.py --batch 16384 \
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_$tag -o prof -f csv -- python3 bench.py --full --batch 16384 \
       --distinct 16384 --steps 8 --warmup 3 --cut-proof 1 --no-cpu --no-detect --no-host-fed --no-b1 --proven-steps 0 \
       --parity-seqs 8 > $O/proven_$tag.log 2>&1 || { echo "$tag failed"; tail -5 $O/proven_$tag.log; exit 1; }
   st=$(find $O/prof_$tag -name "*kernel_stats.csv" | head -1)

@@ -23,7 +23,7 @@ WORKLOAD=${PMC_WORKLOAD:-cfg2}
 PHASE=${PHASE:-all}
 [ "$PHASE" = bench ] || rm -rf $OUT
 mkdir -p $OUT/pmc
-BENCH_ARGS="--steps $STEPS --warmup $WARMUP --workload $WORKLOAD $@"
+BENCH_ARGS="--full --steps $STEPS --warmup $WARMUP --workload $WORKLOAD $@"
 if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 900 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread > $OUT/pytest_gpu.log 2>&1 \
     || { echo "pytest failed"; tail -30 $OUT/pytest_gpu.log; exit 1; }

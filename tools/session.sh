@@ -38,11 +38,11 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 900 python bench.py --steps 20 --warmup 5 $(args "$arg") > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
+      timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 $(args "$arg") > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
       summary $O/bench.log ;;
     quick)
       tag=$(echo "$arg" | tr -c 'a-zA-Z0-9_\n' '_')
-      timeout -k 10 400 python bench.py --steps 5 --warmup 2 --no-cpu --no-detect --no-host-fed --no-b1 $(args "$arg") \
+      timeout -k 10 400 python bench.py --full --steps 5 --warmup 2 --no-cpu --no-detect --no-host-fed --no-b1 $(args "$arg") \
           > $O/quick$tag.log 2>&1 || { tail -5 $O/quick$tag.log; exit 1; }
       summary $O/quick$tag.log ;;
     ab)
@@ -55,14 +55,14 @@ for step in "$@"; do
     profile)
       SKIP_TESTS=1 OUT=$O/profile bash tools/round_profile.sh $(args "$arg") || exit 1 ;;
     rocprof)
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o prof -f csv -- python3 bench.py --steps 5 --warmup 2 \
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/prof -o prof -f csv -- python3 bench.py --full --steps 5 --warmup 2 \
           --no-cpu --no-detect --no-host-fed --no-b1 --parity-seqs 0 $(args "$arg") > $O/rocprof.log 2>&1 \
           || { tail -5 $O/rocprof.log; exit 1; }
       find $O/prof -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \;
       cut -d, -f1-4 $O/kernel_stats.csv | head -14 ;;
     dump)
       tag=$(basename $arg)
-      GFPL_LIB_DIR=$(realpath $arg) timeout -k 10 400 python bench.py --steps 3 --warmup 2 --batch 16384 --distinct 16384 --no-cpu \
+      GFPL_LIB_DIR=$(realpath $arg) timeout -k 10 400 python bench.py --full --steps 3 --warmup 2 --batch 16384 --distinct 16384 --no-cpu \
           --no-detect --no-host-fed --no-b1 --proven-steps 0 --parity-seqs 0 --dump-records $O/dump_$tag.npy \
           > $O/dump_$tag.log 2>&1 || { tail -5 $O/dump_$tag.log; exit 1; }
       summary $O/dump_$tag.log
@@ -70,7 +70,7 @@ for step in "$@"; do
       python3 tools/sp_phases.py $O/dump_${tag}_clk.npy || true ;;
     fullparity)
       tag=$(echo "$arg" | tr -c 'a-zA-Z0-9_\n' '_')
-      timeout -k 10 900 python -u bench.py --steps 3 --warmup 2 --parity-seqs -1 --no-cpu --no-detect --no-host-fed \
+      timeout -k 10 900 python -u bench.py --full --steps 3 --warmup 2 --parity-seqs -1 --no-cpu --no-detect --no-host-fed \
           --no-b1 --proven-steps 0 $(args "$arg") > $O/fullparity$tag.log 2>&1 || { tail -5 $O/fullparity$tag.log; exit 1; }
       summary $O/fullparity$tag.log ;;
     *) echo "unknown step $step"; exit 2 ;;
