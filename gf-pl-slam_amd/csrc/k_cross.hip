@@ -240,7 +240,9 @@ __global__ void __launch_bounds__(BLOCK, GFPL_CL_WAVES) k_cross_lines(KParams p)
     extern __shared__ __align__(16) unsigned char smem[];
     const int b = blockIdx.x;
     const int cap = p.kl_cap;
-    uint32_t* lut = (uint32_t*)smem;   // (first: a compile-time LDS address, folded into the reads' offsets)
+    // knn2_mfma<.., LUT0 = true> below REQUIRES the table at LDS address 0: first in the dynamic LDS, and
+    // no static __shared__ in this kernel (gfpl_knn.hpp)
+    uint32_t* lut = (uint32_t*)smem;
     uint32_t* tb = lut + knn_lut_dwords<1>();
     int* i12 = (int*)(tb + cap * 8);
     int* d012 = i12 + cap;
@@ -265,7 +267,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_CL_WAVES) k_cross_lines(KParams p)
         __syncthreads();
         // 12: prev queries against curr trains, knn-2 on the matrix cores (gfpl_knn.hpp);
         // 21 (curr queries against prev trains, best index only) from the same distance tiles
-        knn2_mfma<1, true, true>(tb, cap, Sc, DP, Sl, (uint32_t*)i12, (uint32_t*)d112, lut, (uint32_t*)i21);
+        knn2_mfma<1, true, true, true>(tb, cap, Sc, DP, Sl, (uint32_t*)i12, (uint32_t*)d112, lut, (uint32_t*)i21);
         __syncthreads();
         for (int i = tid; i < Sl; i += blockDim.x) {
             const uint32_t k0 = (uint32_t)i12[i], k1 = (uint32_t)d112[i];
@@ -361,7 +363,7 @@ hipError_t launch_cross_points(const KParams& p, hipStream_t s) {
 }
 
 hipError_t launch_cross_lines(const KParams& p, hipStream_t s) {
-    const size_t lds = (size_t)p.kl_cap * 32 + (size_t)p.kl_cap * 16 + 520 * 4 + 64 * 4 + 512 * 4;
+    const size_t lds = (size_t)p.kl_cap * 32 + (size_t)p.kl_cap * 16 + 520 * 4 + 64 * 4 + knn_lut_dwords<1>() * 4;
     // large-capacity LDS layout (one workgroup per CU) and small batches: 16 waves
     if (p.kl_cap > 1024 || p.B <= sp_wide_max_b())
         hipLaunchKernelGGL(k_cross_lines<1024>, dim3(p.B), dim3(1024), lds, s, p);

@@ -979,7 +979,9 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SL_WAVES) k_stereo_lines(KParams p
     extern __shared__ __align__(16) unsigned char smem[];
     const int b = blockIdx.x;
     const int cap = p.kl_cap;
-    uint32_t* lut = (uint32_t*)smem;   // (first: a compile-time LDS address, folded into the reads' offsets)
+    // knn2_mfma<.., LUT0 = true> below REQUIRES the table at LDS address 0: first in the dynamic LDS, and
+    // no static __shared__ in this kernel (gfpl_knn.hpp)
+    uint32_t* lut = (uint32_t*)smem;
     uint32_t* tb = lut + knn_lut_dwords<CELL>();
     int* lr_i = (int*)(tb + cap * 8);
     int* lr_d0 = lr_i + cap;
@@ -1006,7 +1008,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SL_WAVES) k_stereo_lines(KParams p
     SL_CLK(1);
     // L->R knn-2 on the matrix cores (gfpl_knn.hpp): keys (dist << 16 | iR); the R->L knn
     // (only its best index is used) from the same distance tiles (RL)
-    knn2_mfma<CELL, true, true>(tb, cap, NR, DLg, NL, (uint32_t*)lr_i, (uint32_t*)lr_d1, lut, (uint32_t*)rl_i);
+    knn2_mfma<CELL, true, true, true>(tb, cap, NR, DLg, NL, (uint32_t*)lr_i, (uint32_t*)lr_d1, lut, (uint32_t*)rl_i);
     __syncthreads();
     SL_CLK(2);
     SL_PRIO(1);
@@ -1280,7 +1282,8 @@ hipError_t launch_stereo_points(const KParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-size_t stereo_lines_lds(int cap) { return (size_t)cap * 32 + (size_t)cap * 16 + 260 * 4 + 64 * 4 + 1024 * 4; }
+// (the table of CELL 2, the larger one, for both instantiations)
+size_t stereo_lines_lds(int cap) { return (size_t)cap * 32 + (size_t)cap * 16 + 260 * 4 + 64 * 4 + knn_lut_dwords<2>() * 4; }
 
 hipError_t launch_stereo_lines(const KParams& p, hipStream_t s) {
     // large-capacity LDS layout (one workgroup per CU) and small batches: 16 waves
