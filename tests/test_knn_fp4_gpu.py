@@ -4,7 +4,9 @@ gfpl_knn2_hamming (k_knn2m) over every pair of the tile-edge sizes, for NORM_HAM
 NORM_HAMMING2 (cell 2): both indices and both distances must be equal as integers — the FP4 operands
 hold only 0 and +-1 and the f32 accumulator counts exactly, so nothing is approximate.  The in-kernel
 passes (knn2_mfma with its reverse direction, inside k_stereo_lines and k_cross_lines) are compared
-through frameStep with the CPU oracle on the bench workload's shapes.
+through frameStep with the CPU oracle on the bench workload's shapes here, and on their own, on
+adversarial line descriptors (ties, duplicates, zero rows, tile-edge counts) against numpy, in
+test_line_match_gpu.py.
 """
 import numpy as np
 import pytest
