@@ -21,7 +21,7 @@ HIP_HDR  := $(wildcard $(PKG)/csrc/*.hpp) include/gfpl.h
 BINDIR   := $(PKG)/bin
 
 all: $(LIBDIR)/libgfpl_hip.so $(LIBDIR)/libgfpl_synth.so oracle/liboracle.so $(LIBDIR)/libgfpl_stvo.so $(BINDIR)/plslam_gpu \
-     $(BINDIR)/mirror_maphandler
+     $(BINDIR)/mirror_maphandler $(BINDIR)/mirror_rectify
 
 $(LIBDIR)/libgfpl_hip.so: $(HIP_SRC) $(HIP_HDR)
 	@mkdir -p $(LIBDIR)
@@ -47,6 +47,12 @@ $(BINDIR)/mirror_maphandler: tests/mirror_maphandler.cpp $(LIBDIR)/libgfpl_stvo.
 	$(CXX) -O2 -std=c++17 -ffp-contract=off -Wall -Iinclude $< -o $@ -L$(LIBDIR) -lgfpl_stvo -lgfpl_hip -l:libgfpl_synth.so -lpthread \
 	    -Wl,-rpath,'$$ORIGIN/../lib'
 
+# a caller of the mirror's PinholeStereoCamera::rectifyImagesLR (tests/test_rectify_mirror.py)
+$(BINDIR)/mirror_rectify: tests/mirror_rectify.cpp $(LIBDIR)/libgfpl_stvo.so
+	@mkdir -p $(BINDIR)
+	$(CXX) -O2 -std=c++17 -ffp-contract=off -Wall -Iinclude $< -o $@ -L$(LIBDIR) -lgfpl_stvo -lgfpl_hip -lpthread \
+	    -Wl,-rpath,'$$ORIGIN/../lib'
+
 ORACLE_SRC := oracle/gfpl_oracle.cpp oracle/gfpl_orb_oracle.cpp oracle/gfpl_lbd_oracle.cpp oracle/gfpl_lsd_oracle.cpp
 oracle/liboracle.so: $(ORACLE_SRC) oracle/gfpl_oracle.h include/gfpl.h $(PKG)/csrc/gfpl_orb_pattern.h
 	$(CXX) $(ORACLEFLAGS) $(ORACLE_SRC) -o $@
@@ -66,9 +72,9 @@ oracle-asan: oracle/build/asan_driver
 oracle: oracle/liboracle.so
 synth: $(LIBDIR)/libgfpl_synth.so
 hip: $(LIBDIR)/libgfpl_hip.so
-host: $(LIBDIR)/libgfpl_stvo.so $(BINDIR)/plslam_gpu $(BINDIR)/mirror_maphandler
+host: $(LIBDIR)/libgfpl_stvo.so $(BINDIR)/plslam_gpu $(BINDIR)/mirror_maphandler $(BINDIR)/mirror_rectify
 
 clean:
-	rm -f $(LIBDIR)/*.so oracle/liboracle.so $(BINDIR)/plslam_gpu $(BINDIR)/mirror_maphandler oracle/build/asan_driver
+	rm -f $(LIBDIR)/*.so oracle/liboracle.so $(BINDIR)/plslam_gpu $(BINDIR)/mirror_maphandler $(BINDIR)/mirror_rectify oracle/build/asan_driver
 
 .PHONY: all clean oracle oracle-asan synth hip host

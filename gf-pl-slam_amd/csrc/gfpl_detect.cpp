@@ -15,7 +15,9 @@
 // both images on one, LSD of both images (one 2B-image call: the latency-bound region growth
 // wants every image in flight) then LBD of both on the other; the ORB stream joins the line
 // stream before the set's `ready` event.  The input images are first copied into the set's
-// image buffer ([left B | right B], the layout one LSD call reads).  Every gfpl_frames view
+// image buffer ([left B | right B], the layout one LSD call reads).
+// With a rectifier attached (gfpl_detector_set_rectifier) the inputs are raw camera images and
+// that copy is the remap (k_rectify.hip) into the same buffer.  Every gfpl_frames view
 // carries `ready` (detection done) and `consumed` (recorded by the tracker call that reads
 // it), so the next detection into the same buffer set waits for exactly that read.
 #include <hip/hip_runtime.h>
@@ -75,6 +77,8 @@ struct gfpl_detector {
     int B = 0, kp_cap = 0, kl_cap = 0, sets = 0, W = 0, H = 0;
     int64_t pyr_bytes = 0;
     void* base = nullptr;
+    gfpl_rectifier* rect = nullptr;   // attached: the inputs are raw images, rectified into the set
+    uint8_t* raw = nullptr;           // [2B][H][W] staging of raw HOST images (allocated when a rectifier is attached)
     DetSet set[kMaxSets];
     int64_t k = 0;
 };
@@ -92,6 +96,7 @@ void teardown(gfpl_detector* d) {
             if (e) gfpl_event_destroy(e);
     if (d->inputs) gfpl_event_destroy(d->inputs);
     if (d->base) (void)hipFree(d->base);
+    if (d->raw) (void)hipFree(d->raw);
     if (d->c_orb) gfpl_destroy(d->c_orb);
     if (d->c_lines) gfpl_destroy(d->c_lines);
     if (d->ctx) gfpl_ctx_detach(d->ctx);
@@ -269,8 +274,12 @@ int gfpl_detect_stereo_async(gfpl_detector* d, const uint8_t* img_l, const uint8
     DET_CHK(begin(d, n, &S));
     const size_t bytes = (size_t)n * d->W * d->H;
     hipStream_t s = (hipStream_t)gfpl_get_stream(d->c_lines);
-    DET_HIPCHK(hipMemcpyAsync(S->img, img_l, bytes, hipMemcpyDeviceToDevice, s));
-    DET_HIPCHK(hipMemcpyAsync(S->img + bytes, img_r, bytes, hipMemcpyDeviceToDevice, s));
+    if (d->rect) {
+        DET_CHK(gfpl_rectifier_enqueue(d->rect, s, 0, img_l, img_r, n, S->img, S->img + bytes));
+    } else {
+        DET_HIPCHK(hipMemcpyAsync(S->img, img_l, bytes, hipMemcpyDeviceToDevice, s));
+        DET_HIPCHK(hipMemcpyAsync(S->img + bytes, img_r, bytes, hipMemcpyDeviceToDevice, s));
+    }
     DET_HIPCHK(hipMemcpyAsync(S->ts, time_stamp, 8 * (size_t)n, hipMemcpyDeviceToDevice, s));
     return run(d, *S, n, out);
 }
@@ -282,12 +291,38 @@ int gfpl_detect_stereo_host(gfpl_detector* d, const uint8_t* img_l, const uint8_
     DET_CHK(begin(d, n, &S));
     const size_t bytes = (size_t)n * d->W * d->H;
     hipStream_t s = (hipStream_t)gfpl_get_stream(d->c_lines);
-    DET_HIPCHK(hipMemcpyAsync(S->img, img_l, bytes, hipMemcpyHostToDevice, s));
-    DET_HIPCHK(hipMemcpyAsync(S->img + bytes, img_r, bytes, hipMemcpyHostToDevice, s));
+    if (d->rect) {
+        // raw images: staged on the device, then rectified into the set (the staging buffer is
+        // reused by the next call, ordered after this remap on the same stream)
+        DET_HIPCHK(hipMemcpyAsync(d->raw, img_l, bytes, hipMemcpyHostToDevice, s));
+        DET_HIPCHK(hipMemcpyAsync(d->raw + bytes, img_r, bytes, hipMemcpyHostToDevice, s));
+        DET_CHK(gfpl_rectifier_enqueue(d->rect, s, 0, d->raw, d->raw + bytes, n, S->img, S->img + bytes));
+    } else {
+        DET_HIPCHK(hipMemcpyAsync(S->img, img_l, bytes, hipMemcpyHostToDevice, s));
+        DET_HIPCHK(hipMemcpyAsync(S->img + bytes, img_r, bytes, hipMemcpyHostToDevice, s));
+    }
     DET_HIPCHK(hipMemcpyAsync(S->ts, time_stamp, 8 * (size_t)n, hipMemcpyHostToDevice, s));
     // the caller's host buffers may change once this returns
     DET_HIPCHK(hipStreamSynchronize(s));
     return run(d, *S, n, out);
+}
+
+int gfpl_detector_set_rectifier(gfpl_detector* d, gfpl_rectifier* r) {
+    if (!d) return GFPL_E_INVALID;
+    if (r && (gfpl_rectifier_width(r) != d->W || gfpl_rectifier_height(r) != d->H)) return GFPL_E_INVALID;
+    if (r && !d->raw) {
+        const size_t bytes = 2 * (size_t)d->B * d->W * d->H;
+        if (hipSetDevice(gfpl_ctx_device(d->ctx)) != hipSuccess) return GFPL_E_HIP;
+        if (hipMalloc((void**)&d->raw, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            d->raw = nullptr;
+            std::fprintf(stderr, "gfpl_detector_set_rectifier: device allocation of %zu bytes failed\n", bytes);
+            return GFPL_E_NOMEM;
+        }
+    }
+    // detections already enqueued keep reading the maps they were launched with
+    d->rect = r;
+    return GFPL_OK;
 }
 
 int gfpl_detector_status(gfpl_detector* d) {

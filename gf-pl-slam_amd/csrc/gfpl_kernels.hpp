@@ -92,6 +92,12 @@ void gfpl_ctx_attach(gfpl_ctx* c);
 void gfpl_ctx_detach(gfpl_ctx* c);
 // how often the event was recorded (gfpl_event_record, or as a tracker call's gfpl_frames.consumed)
 int64_t gfpl_event_records(const gfpl_event* e);
+// the rectifier (k_rectify.hip) for the detector: its image size, and one launch on the given
+// stream: both sides when src_r / dst_r are given, else `side` alone
+int gfpl_rectifier_width(const gfpl_rectifier* r);
+int gfpl_rectifier_height(const gfpl_rectifier* r);
+int gfpl_rectifier_enqueue(gfpl_rectifier* r, void* stream, int side, const uint8_t* src_l, const uint8_t* src_r,
+                           int n, uint8_t* dst_l, uint8_t* dst_r);
 
 namespace gfpl {
 // Deferred error status of the stream-ordered detector calls (gfpl_*_async): the kernels

@@ -96,6 +96,7 @@ extern "C" const char* gfpl_strerror(int code) {
         case GFPL_E_CAPACITY: return "feature count exceeds seqbatch capacity";
         case GFPL_E_STATE: return "call order violated";
         case GFPL_E_UNSUPPORTED: return "config flag combination not implemented";
+        case GFPL_E_NOMEM: return "device memory allocation failed";
         default: return "unknown error";
     }
 }

@@ -32,7 +32,7 @@ HAMMING, HAMMING2 = 1, 2
 
 ERRORS = {0: "ok", -1: "invalid argument", -2: "HIP runtime error", -3: "no HIP device",
           -4: "knn-2 needs at least 2 train descriptors", -5: "capacity exceeded",
-          -6: "call order violated", -7: "unsupported config"}
+          -6: "call order violated", -7: "unsupported config", -8: "device memory allocation failed"}
 
 
 class GfplError(RuntimeError):
@@ -244,6 +244,28 @@ class DetectionsHost(C.Structure):
                 ("kl_l", _vp), ("kl_r", _vp), ("ldesc_l", _vp), ("ldesc_r", _vp)]
 
 
+class RectifySide(C.Structure):
+    """gfpl_rectify_side: one camera of the rig as PinholeStereoCamera's distortion constructors take
+    it (src/pinholeStereoCamera.cpp:49-94): raw K (fx fy cx cy), distortion D, rectifying R (row-major
+    3x3) and the rectified P (fx fy cx cy); model 0 = pinhole radial-tangential, 1 = equidistant."""
+    _fields_ = [("model", C.c_int), ("K", C.c_double * 4), ("D", C.c_double * 8), ("n_dist", C.c_int),
+                ("R", C.c_double * 9), ("P", C.c_double * 4)]
+
+    @classmethod
+    def make(cls, K, D, R, P, equi: bool = False) -> "RectifySide":
+        s = cls()
+        D = [float(v) for v in np.asarray(D, np.float64).reshape(-1)]
+        if len(D) > 8:
+            raise GfplError(-7, f"{len(D)} distortion coefficients")
+        s.model = 1 if equi else 0
+        s.K[:] = [float(v) for v in np.asarray(K, np.float64).reshape(-1)]
+        s.D[:len(D)] = D
+        s.n_dist = len(D)
+        s.R[:] = [float(v) for v in np.asarray(R, np.float64).reshape(-1)]
+        s.P[:] = [float(v) for v in np.asarray(P, np.float64).reshape(-1)]
+        return s
+
+
 class SynthParams(C.Structure):
     _fields_ = [("n_kp", C.c_int), ("n_kl", C.c_int), ("n_world_pts", C.c_int),
                 ("n_world_lines", C.c_int), ("dt", C.c_double), ("v_fwd", C.c_double),
@@ -379,6 +401,15 @@ def hiplib() -> C.CDLL:
             "gfpl_detector_status": ([P], C.c_int),
             "gfpl_detector_discard": ([P, P], C.c_int),
             "gfpl_read_detections": ([P, P, C.c_int, P], C.c_int),
+            "gfpl_rectify_maps_host": ([P, C.c_int, C.c_int, P, P], C.c_int),
+            "gfpl_rectifier_create": ([P, P, P, C.c_int, C.c_int, C.POINTER(P)], C.c_int),
+            "gfpl_rectifier_destroy": ([P], C.c_int),
+            "gfpl_rectifier_read_maps": ([P, C.c_int, P, P], C.c_int),
+            "gfpl_rectify": ([P, C.c_int, P, C.c_int, P], C.c_int),
+            "gfpl_rectify_async": ([P, C.c_int, P, C.c_int, P], C.c_int),
+            "gfpl_rectify_stereo_async": ([P, P, P, C.c_int, P, P], C.c_int),
+            "gfpl_rectify_host": ([P, C.c_int, P, C.c_int, P], C.c_int),
+            "gfpl_detector_set_rectifier": ([P, P], C.c_int),
         }
         for n, (a, r) in sigs.items():
             try:
@@ -1355,6 +1386,72 @@ class BinaryDescriptor:
             pass
 
 
+def rectify_maps(side: RectifySide, width: int, height: int):
+    """gfpl_rectify_maps_host: the CV_16SC2 + CV_16UC1 maps of one camera, built on the host
+    (no device needed).  Returns (map1 int16 [H][W][2] (x, y), map2 uint16 [H][W])."""
+    if width < 1 or height < 1:
+        raise GfplError(-1, "rectify_maps_host")
+    map1 = np.zeros((height, width, 2), np.int16)
+    map2 = np.zeros((height, width), np.uint16)
+    check(hiplib().gfpl_rectify_maps_host(C.byref(side), width, height, map1.ctypes.data, map2.ctypes.data),
+          "rectify_maps_host")
+    return map1, map2
+
+
+class StereoRectifier:
+    """gfpl_rectifier: PinholeStereoCamera::rectifyImage / rectifyImagesLR
+    (src/pinholeStereoCamera.cpp:96-119) for batches of 8-bit images on the device: the maps of
+    both cameras are built on the host (ledger R1-R5) and uploaded once; rectify() is
+    cv::remap(INTER_LINEAR, BORDER_CONSTANT 0) with them (R6), enqueued on the context's stream."""
+
+    def __init__(self, left: RectifySide, right: RectifySide, width: int, height: int, ctx: Context):
+        self.L = ctx.L
+        self.ctx, self.width, self.height = ctx, width, height
+        self.left, self.right = left, right
+        h = C.c_void_p()
+        check(self.L.gfpl_rectifier_create(ctx.h, C.byref(left), C.byref(right), width, height, C.byref(h)),
+              "rectifier_create")
+        self.h = h
+
+    def rectify(self, side: int, src, n: int, out, sync: bool = False) -> None:
+        """src / out: device u8 [n][H][W] (distinct buffers); side 0 = left, 1 = right"""
+        f = self.L.gfpl_rectify if sync else self.L.gfpl_rectify_async
+        check(f(self.h, side, _ptr(src), n, _ptr(out)), "rectify")
+
+    def rectify_stereo(self, src_l, src_r, n: int, out_l, out_r) -> None:
+        """rectifyImagesLR for n stereo frames: both sides in one launch"""
+        check(self.L.gfpl_rectify_stereo_async(self.h, _ptr(src_l), _ptr(src_r), n, _ptr(out_l), _ptr(out_r)),
+              "rectify_stereo_async")
+
+    def rectify_host(self, side: int, images: np.ndarray) -> np.ndarray:
+        """rectifyImage on HOST images [n][H][W] (or one [H][W]) u8; returns the rectified copy"""
+        src = np.ascontiguousarray(images, np.uint8)
+        if src.shape[-2:] != (self.height, self.width):
+            raise ValueError(f"images {src.shape} != (..., {self.height}, {self.width})")
+        out = np.empty_like(src)
+        n = 1 if src.ndim == 2 else int(np.prod(src.shape[:-2]))
+        check(self.L.gfpl_rectify_host(self.h, side, src.ctypes.data, n, out.ctypes.data), "rectify_host")
+        return out
+
+    def maps(self, side: int):
+        """the uploaded maps of one side, read back: (map1 int16 [H][W][2], map2 uint16 [H][W])"""
+        map1 = np.zeros((self.height, self.width, 2), np.int16)
+        map2 = np.zeros((self.height, self.width), np.uint16)
+        check(self.L.gfpl_rectifier_read_maps(self.h, side, map1.ctypes.data, map2.ctypes.data), "rectifier_read_maps")
+        return map1, map2
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gfpl_rectifier_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class StereoDetector:
     """gfpl_detector: StereoFrame's detection from a stereo pair of images on the device —
     ORB of both images (the right pyramid kept for the sub-pixel refinement), LSD with the
@@ -1396,6 +1493,12 @@ class StereoDetector:
         check(self.L.gfpl_detect_stereo_host(self.h, left.ctypes.data, right.ctypes.data, n, ts.ctypes.data,
                                              C.byref(fr)), "detect_stereo_host")
         return fr
+
+    def set_rectifier(self, rectifier: Optional["StereoRectifier"]) -> None:
+        """gfpl_detector_set_rectifier: detect() / detect_host() then take raw images (None detaches)"""
+        check(self.L.gfpl_detector_set_rectifier(self.h, rectifier.h if rectifier is not None else None),
+              "detector_set_rectifier")
+        self._rectifier = rectifier
 
     def status(self) -> None:
         check(self.L.gfpl_detector_status(self.h), "detector_status")

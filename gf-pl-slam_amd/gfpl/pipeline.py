@@ -19,7 +19,7 @@ import functools
 import numpy as np
 
 from . import (DESC, KEYLINE_DT, KEYPOINT_DT, BinaryDescriptor, Context, Event, LSDDetector, LsdParams,
-               ORBextractor, make_frames, synth_image, synth_keylines)
+               ORBextractor, StereoRectifier, make_frames, synth_image, synth_keylines)
 
 
 def _draw_bars(img: np.ndarray, n: int, seed: int) -> np.ndarray:
@@ -158,14 +158,20 @@ class ImagePipeline:
     outstanding: detecting into a set whose last view no tracker call has read yet raises
     (discard() releases a view that will not be tracked).  Capacity / octave errors of the
     asynchronous detectors are reported by status(); device outputs are complete after
-    synchronize() (status() waits for the detectors' own status words only)."""
+    synchronize() (status() waits for the detectors' own status words only).
+
+    rectifier: a StereoRectifier of the camera's image size; detect() / detect_images() then take
+    RAW images, rectified (PinholeStereoCamera::rectifyImagesLR, app/plslam_mod.cpp:348-351) on
+    the detection stream into the set's image buffer, which every detector reads."""
 
     def __init__(self, ctx: Context, cam, batch: int, kl_cap: int, nfeatures: int = 2000, lsd: bool = False,
-                 cfg=None, sets: int = 2):
+                 cfg=None, sets: int = 2, rectifier=None):
         import torch
         cfg = cfg if cfg is not None else ctx.cfg
         self.ctx, self.cam, self.B, self.kl_cap, self.sets = ctx, cam, batch, kl_cap, sets
         W, H = int(cam.width), int(cam.height)
+        if rectifier is not None and (rectifier.width, rectifier.height) != (W, H):
+            raise ValueError(f"rectifier {rectifier.width} x {rectifier.height} != camera {W} x {H}")
         # the detection stream is a torch stream (pooled by torch, never destroyed), so torch's
         # allocator may record the inputs' use on it (Tensor.record_stream)
         self._tstream = torch.cuda.Stream(device=torch.device("cuda", ctx.device))
@@ -185,6 +191,10 @@ class ImagePipeline:
         self.lsd = LSDDetector(W, H, LsdParams.reference(W, H), max_images=2 * batch, kl_cap=kl_cap,
                                ctx=self.det) if lsd else None
         self.kp_cap = self.orb.kp_cap
+        self.rect = None
+        if rectifier is not None:
+            # the same maps on the detection stream's context (the remap is enqueued there)
+            self.rect = StereoRectifier(rectifier.left, rectifier.right, W, H, self.det)
         dev = torch.device("cuda", ctx.device)
         B, kc = batch, self.kp_cap
         z = lambda n, dt=torch.uint8: torch.zeros(n, dtype=dt, device=dev)
@@ -198,7 +208,7 @@ class ImagePipeline:
                 "pdesc": [z(B * kc * DESC), z(B * kc * DESC)],
                 "n_kl_lr": n_kl_lr, "kl_lr": kl_lr,
                 "n_kl": [n_kl_lr[:B], n_kl_lr[B:]], "kl": [kl_lr[:kls], kl_lr[kls:]],
-                "img_lr": z(2 * B * W * H) if lsd else None,
+                "img_lr": z(2 * B * W * H) if lsd or self.rect is not None else None,
                 "ldesc": [z(B * kl_cap * DESC), z(B * kl_cap * DESC)],
                 "pyr_l": z(B * int(cam.pyr_bytes)),   # the left pyramid (not read by the tracker)
                 "pyr_r": z(B * int(cam.pyr_bytes)),
@@ -206,6 +216,7 @@ class ImagePipeline:
         self.ready = [Event(self.det) for _ in range(sets)]
         self.orb_done = [Event(self.det_orb) for _ in range(sets)]
         self.consumed = [Event(ctx) for _ in range(sets)]
+        self.rectified = [Event(self.det) for _ in range(sets)] if self.rect is not None else None
         self.k = 0
         self._handed = [None] * sets   # consumed[s].record_count when set s's view was returned
         torch.cuda.synchronize(dev)   # the buffers' zero fills (default stream) before any detection
@@ -230,6 +241,17 @@ class ImagePipeline:
                 t.record_stream(st)   # the caching allocator keeps them until the detection ran
         return s, ts
 
+    def _rectify(self, s, left, right):
+        """raw images -> the set's image buffer on the detection stream (after _begin's waits); the
+        ORB stream waits for it.  Returns the rectified left / right halves."""
+        b = self.bufs[s]
+        n = self.B * int(self.cam.width) * int(self.cam.height)
+        rl, rr = b["img_lr"][:n], b["img_lr"][n:]
+        self.rect.rectify_stereo(left, right, self.B, rl, rr)
+        self.rectified[s].record(self.det)
+        self.rectified[s].wait(self.det_orb)
+        return rl, rr
+
     def detect(self, left, right, kl_left, n_kl_left, kl_right, n_kl_right, time_stamp):
         """left / right: device u8 [B][H][W]; kl_*: device KEYLINE_DT rows [B][kl_cap];
         n_kl_*: device int32 [B]; time_stamp: device f64 [B].  Returns the gfpl_frames
@@ -241,6 +263,8 @@ class ImagePipeline:
             for side, (kl, n) in enumerate(((kl_left, n_kl_left), (kl_right, n_kl_right))):
                 b["kl"][side].copy_(kl.view(-1))
                 b["n_kl"][side].copy_(n)
+        if self.rect is not None:
+            left, right = self._rectify(s, left, right)
         return self._describe(s, ts, left, right, time_stamp)
 
     def detect_images(self, left, right, time_stamp):
@@ -253,9 +277,12 @@ class ImagePipeline:
         s, ts = self._begin([left, right, time_stamp])
         b = self.bufs[s]
         n = self.B * int(self.cam.width) * int(self.cam.height)
-        with torch.cuda.stream(ts):
-            b["img_lr"][:n].copy_(left.reshape(-1))
-            b["img_lr"][n:].copy_(right.reshape(-1))
+        if self.rect is not None:
+            left, right = self._rectify(s, left, right)
+        else:
+            with torch.cuda.stream(ts):
+                b["img_lr"][:n].copy_(left.reshape(-1))
+                b["img_lr"][n:].copy_(right.reshape(-1))
         self.lsd.detect_async(b["img_lr"], 2 * self.B, b["kl_lr"], b["n_kl_lr"])
         return self._describe(s, ts, left, right, time_stamp)
 
@@ -306,7 +333,9 @@ class ImagePipeline:
         self.lbd.close()
         if self.lsd is not None:
             self.lsd.close()
-        for e in self.ready + self.orb_done + self.consumed:
+        if self.rect is not None:
+            self.rect.close()
+        for e in self.ready + self.orb_done + self.consumed + (self.rectified or []):
             e.close()
         self.det.close()
         self.det_orb.close()

@@ -1,15 +1,22 @@
 // plslam_gpu.cpp — the per-frame loop of app/plslam_mod.cpp:318-515 over the
-// StVO host mirror, GPU only: on a directory of rectified grey stereo images
+// StVO host mirror, GPU only: on a directory of grey stereo images, rectified already or
+// raw with the rig's calibration (--rectify: app/plslam_mod.cpp:82-131, 348-351)
 // (--images: detection on the GPU, the reference's insertStereoPair(img_l, img_r,
 // idx, ts) signature) or on synthetic stereo detections (gfpl_synth).
 //
 //   plslam_gpu [--camera vga|euroc|kitti|stress] [--frames N] [--seq S] [--out PREFIX] [--json]
-//              [--images DIR] [--orb-features N]
+//              [--images DIR] [--orb-features N] [--rectify FILE]
 //
 // --images DIR reads DIR/left/%06d.pgm and DIR/right/%06d.pgm (binary 8-bit PGM of the
 // camera's size; the reference's app reads its dataset through cv::imread) for frames
 // 0..N-1 (stopping at the first missing pair) and the time stamps from DIR/times.txt
 // (one per line; absent: 0.05 s per frame).
+// --rectify FILE (with --images): the images are raw; FILE holds the rig's eight arrays, one
+// "key: values" line each: Kl Kr (fx fy cx cy), Dl Dr (4, 5 or 8 coefficients), Rl Rr (9),
+// Pl Pr (fx fy cx cy of the rectified cameras), optionally "equi: 1".  Every pair goes through
+// PinholeStereoCamera::rectifyImagesLR before the tracker sees it, and the tracked camera's
+// intrinsics are Pl's; Kl and Kr are rounded through float first, as the reference's app
+// builds them as Mat_<float> (app/plslam_mod.cpp:90-91).
 //
 // Per frame: initialize (frame 0) or insertStereoPair -> optimizePose(prev_frame->DT)
 // -> numFrameLoss check -> needNewKF / currFrameIsKF -> updateFrame_ECCV18(T_base),
@@ -137,7 +144,7 @@ static std::string frame_name(const std::string& dir, const char* side, int k) {
 }
 
 static int run(int argc, char** argv) {
-    std::string camname = "vga", out, images;
+    std::string camname = "vga", out, images, rectify;
     int frames = 10, seq = 0, orb_features = 0;
     bool json = false;
     for (int i = 1; i < argc; ++i) {
@@ -153,6 +160,7 @@ static int run(int argc, char** argv) {
         else if (a == "--json") json = true;
         else if (a == "--images") images = next();
         else if (a == "--orb-features") orb_features = std::stoi(next());
+        else if (a == "--rectify") rectify = next();
         else { std::cerr << "unknown option " << a << "\n"; return 2; }
     }
     const CamDef* cd = nullptr;
@@ -160,6 +168,14 @@ static int run(int argc, char** argv) {
         if (camname == c.name) cd = &c;
     if (!cd) { std::cerr << "unknown camera " << camname << "\n"; return 2; }
     PinholeStereoCamera cam(cd->w, cd->h, cd->fx, cd->fy, cd->cx, cd->cy, cd->b);
+    if (!rectify.empty()) {
+        if (images.empty()) { std::cerr << "--rectify needs --images\n"; return 2; }
+        const RectifyFile rf = RectifyFile::read(rectify);
+        double Kl[4], Kr[4];
+        for (int i = 0; i < 4; ++i) { Kl[i] = (double)(float)rf.Kl[i]; Kr[i] = (double)(float)rf.Kr[i]; }
+        cam = PinholeStereoCamera(cd->w, cd->h, cd->b, Kl, Kr, rf.Rl.data(), rf.Rr.data(), rf.Pl.data(), rf.Pr.data(),
+                                  rf.Dl, rf.Dr, rf.equi);
+    }
     gfpl_synth_params sp;
     gfpl_synth_default(&sp);
     if (camname == "kitti") { sp.dt = 0.1; sp.v_fwd = 8.0; sp.z_min = 4.0; sp.z_max = 40.0; }
@@ -190,9 +206,15 @@ static int run(int argc, char** argv) {
         if (images.empty()) {
             f = make_frame(sp, &cam, seq, k, kp_cap, kl_cap);
         } else {
-            const std::vector<uint8_t> L = read_pgm(frame_name(images, "left", k), cd->w, cd->h);
-            const std::vector<uint8_t> R = read_pgm(frame_name(images, "right", k), cd->w, cd->h);
+            std::vector<uint8_t> L = read_pgm(frame_name(images, "left", k), cd->w, cd->h);
+            std::vector<uint8_t> R = read_pgm(frame_name(images, "right", k), cd->w, cd->h);
             if (L.empty() || R.empty()) break;
+            if (!rectify.empty()) {   // cam_pin->rectifyImagesLR(img_l, img_l, img_r, img_r) (:348-351)
+                std::vector<uint8_t> Lr, Rr;
+                cam.rectifyImagesLR(L, Lr, R, Rr);
+                L.swap(Lr);
+                R.swap(Rr);
+            }
             const double ts = k < (int)times.size() ? times[k] : 0.05 * k;
             f = new StereoFrame(L.data(), R.data(), k, &cam, ts);   // = insertStereoPair(img_l, img_r, k, ts)
         }

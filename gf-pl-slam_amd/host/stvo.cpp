@@ -5,8 +5,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <fstream>
 #include <map>
 #include <memory>
+#include <sstream>
 #include <unordered_map>
 
 namespace StVO {
@@ -151,7 +153,134 @@ void BFMatcher::radiusMatch(const std::vector<Descriptor>& query, const std::vec
 }
 
 // ---------------------------------------------- StereoFrame frame members --
-PinholeStereoCamera::~PinholeStereoCamera() = default;   // (StereoFrameHandler complete here)
+PinholeStereoCamera::~PinholeStereoCamera() { dropRectifier(); }   // (StereoFrameHandler complete here)
+
+namespace {
+
+gfpl_rectify_side rect_side(bool equi, const double K[4], const std::vector<double>& D, const double R[9],
+                            const double P[4]) {
+    if (D.size() > 8) throw std::runtime_error("PinholeStereoCamera: more than 8 distortion coefficients");
+    gfpl_rectify_side s{};
+    s.model = equi ? 1 : 0;
+    std::copy(K, K + 4, s.K);
+    std::copy(D.begin(), D.end(), s.D);
+    s.n_dist = (int)D.size();
+    std::copy(R, R + 9, s.R);
+    std::copy(P, P + 4, s.P);
+    return s;
+}
+
+void rect_check(int rc, const char* what) {
+    if (rc != GFPL_OK) throw std::runtime_error(std::string(what) + ": " + gfpl_strerror(rc));
+}
+
+}  // namespace
+
+PinholeStereoCamera::PinholeStereoCamera(int width, int height, double fx, double fy, double cx, double cy, double b,
+                                         const double Rl[9], const double Rr[9], const double Pl[4],
+                                         const double Pr[4], double d0, double d1, double d2, double d3, double d4)
+    : PinholeStereoCamera(width, height, fx, fy, cx, cy, b) {
+    dist_ = d0 != 0.0;
+    const double K[4] = {fx, fy, cx, cy};
+    const std::vector<double> D = {d0, d1, d2, d3, d4};
+    side_[0] = rect_side(false, K, D, Rl, Pl);
+    side_[1] = rect_side(false, K, D, Rr, Pr);
+}
+
+PinholeStereoCamera::PinholeStereoCamera(int width, int height, double b, const double Kl[4], const double Kr[4],
+                                         const double Rl[9], const double Rr[9], const double Pl[4],
+                                         const double Pr[4], const std::vector<double>& Dl,
+                                         const std::vector<double>& Dr, bool equi)
+    : PinholeStereoCamera(width, height, Pl[0], Pl[1], Pl[2], Pl[3], b) {
+    dist_ = true;
+    side_[0] = rect_side(equi, Kl, Dl, Rl, Pl);
+    side_[1] = rect_side(equi, Kr, Dr, Rr, Pr);
+}
+
+gfpl_rectifier* PinholeStereoCamera::rectifier() const {
+    std::lock_guard<std::mutex> lk(rect_mu_);
+    if (!rect_) {
+        if (!rect_ctx_) rect_check(gfpl_create(0, nullptr, &rect_ctx_), "gfpl_create");
+        rect_check(gfpl_rectifier_create(rect_ctx_, &side_[0], &side_[1], cam_.width, cam_.height, &rect_),
+                   "gfpl_rectifier_create");
+    }
+    return rect_;
+}
+
+void PinholeStereoCamera::dropRectifier() {
+    std::lock_guard<std::mutex> lk(rect_mu_);
+    if (rect_) gfpl_rectifier_destroy(rect_);
+    if (rect_ctx_) gfpl_destroy(rect_ctx_);
+    rect_ = nullptr;
+    rect_ctx_ = nullptr;
+}
+
+void PinholeStereoCamera::rectifyImage(const std::vector<uint8_t>& img_src, std::vector<uint8_t>& img_rec) const {
+    if (img_src.size() != (size_t)cam_.width * cam_.height)
+        throw std::invalid_argument("rectifyImage: image size differs from the camera's");
+    if (!dist_) { img_rec = img_src; return; }   // img_rec = img_src.clone()
+    if (&img_src == &img_rec) throw std::invalid_argument("rectifyImage: in place");
+    img_rec.resize(img_src.size());
+    rect_check(gfpl_rectify_host(rectifier(), 0, img_src.data(), 1, img_rec.data()), "gfpl_rectify_host");
+}
+
+void PinholeStereoCamera::rectifyImagesLR(const std::vector<uint8_t>& img_src_l, std::vector<uint8_t>& img_rec_l,
+                                          const std::vector<uint8_t>& img_src_r,
+                                          std::vector<uint8_t>& img_rec_r) const {
+    const size_t px = (size_t)cam_.width * cam_.height;
+    if (img_src_l.size() != px || img_src_r.size() != px)
+        throw std::invalid_argument("rectifyImagesLR: image size differs from the camera's");
+    if (!dist_) { img_rec_l = img_src_l; img_rec_r = img_src_r; return; }
+    if (&img_src_l == &img_rec_l || &img_src_r == &img_rec_r) throw std::invalid_argument("rectifyImagesLR: in place");
+    img_rec_l.resize(px);
+    img_rec_r.resize(px);
+    rect_check(gfpl_rectify_host(rectifier(), 0, img_src_l.data(), 1, img_rec_l.data()), "gfpl_rectify_host");
+    rect_check(gfpl_rectify_host(rectifier(), 1, img_src_r.data(), 1, img_rec_r.data()), "gfpl_rectify_host");
+}
+
+void PinholeStereoCamera::rectifyImage(const uint8_t* dev_src, uint8_t* dev_rec, int n) const {
+    rect_check(dist_ ? gfpl_rectify(rectifier(), 0, dev_src, n, dev_rec) : GFPL_E_STATE, "gfpl_rectify");
+}
+
+void PinholeStereoCamera::rectifyImagesLR(const uint8_t* dev_src_l, uint8_t* dev_rec_l, const uint8_t* dev_src_r,
+                                          uint8_t* dev_rec_r, int n) const {
+    if (!dist_) rect_check(GFPL_E_STATE, "rectifyImagesLR");
+    gfpl_rectifier* r = rectifier();
+    rect_check(gfpl_rectify_stereo_async(r, dev_src_l, dev_src_r, n, dev_rec_l, dev_rec_r), "gfpl_rectify_stereo_async");
+    rect_check(gfpl_synchronize(rect_ctx_), "gfpl_synchronize");
+}
+
+RectifyFile RectifyFile::read(const std::string& path) {
+    std::ifstream f(path);
+    if (!f) throw std::runtime_error(path + ": cannot open");
+    RectifyFile r;
+    std::string line;
+    while (std::getline(f, line)) {
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line.erase(hash);
+        const size_t colon = line.find(':');
+        if (colon == std::string::npos) continue;
+        std::string key = line.substr(0, colon);
+        key.erase(0, key.find_first_not_of(" \t"));
+        key.erase(key.find_last_not_of(" \t") + 1);
+        std::string rest = line.substr(colon + 1);
+        for (char& c : rest)
+            if (c == ',' || c == '[' || c == ']') c = ' ';
+        std::istringstream is(rest);
+        std::vector<double> v;
+        for (double x; is >> x;) v.push_back(x);
+        if (key == "Kl") r.Kl = v; else if (key == "Kr") r.Kr = v;
+        else if (key == "Dl") r.Dl = v; else if (key == "Dr") r.Dr = v;
+        else if (key == "Rl") r.Rl = v; else if (key == "Rr") r.Rr = v;
+        else if (key == "Pl") r.Pl = v; else if (key == "Pr") r.Pr = v;
+        else if (key == "equi") r.equi = !v.empty() && v[0] != 0.0;
+        else throw std::runtime_error(path + ": unknown key " + key);
+    }
+    if (r.Kl.size() != 4 || r.Kr.size() != 4 || r.Pl.size() != 4 || r.Pr.size() != 4 || r.Rl.size() != 9 ||
+        r.Rr.size() != 9 || r.Dl.empty() || r.Dr.empty() || r.Dl.size() > 8 || r.Dr.size() > 8)
+        throw std::runtime_error(path + ": needs Kl Kr Pl Pr (4 values), Rl Rr (9), Dl Dr (4, 5 or 8)");
+    return r;
+}
 
 StereoFrameHandler& StereoFrame::engine() {
     std::lock_guard<std::mutex> lk(cam->engine_mu_);

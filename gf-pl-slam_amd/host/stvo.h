@@ -168,19 +168,61 @@ private:
 };
 
 // ---------------------------------------------------- PinholeStereoCamera --
-// include/pinholeStereoCamera.h:37-103 (rectified, distortion-free subset).
+// include/pinholeStereoCamera.h:37-103.  The first constructor is the distortion-free camera
+// (dist == false: rectifyImage clones); the other two are the reference's distortion shapes
+// (src/pinholeStereoCamera.cpp:46-94) with the rectified projections Pl / Pr supplied by the
+// caller instead of cv::stereoRectify.  Matrices are plain arrays: K / P = fx fy cx cy,
+// R row-major 3x3.
 class StereoFrameHandler;
+
+// the eight arrays of a rig's calibration as plslam_gpu --rectify reads them: lines
+// "Kl: fx fy cx cy", "Kr:", "Dl: k1 k2 p1 p2 [k3 [k4 k5 k6]]", "Dr:", "Rl: 9 values", "Rr:",
+// "Pl: fx fy cx cy", "Pr:", optionally "equi: 1" (values separated by blanks or commas, '#'
+// starts a comment)
+struct RectifyFile {
+    std::vector<double> Kl, Kr, Dl, Dr, Rl, Rr, Pl, Pr;
+    bool equi = false;
+    static RectifyFile read(const std::string& path);   // throws std::runtime_error
+};
 
 class PinholeStereoCamera {
 public:
     PinholeStereoCamera(int width, int height, double fx, double fy, double cx, double cy, double b);
+    // one K / D for both cameras (:46-60): fx..cy are the raw and the tracked intrinsics,
+    // dist = (d0 != 0)
+    PinholeStereoCamera(int width, int height, double fx, double fy, double cx, double cy, double b,
+                        const double Rl[9], const double Rr[9], const double Pl[4], const double Pr[4],
+                        double d0, double d1 = 0.0, double d2 = 0.0, double d3 = 0.0, double d4 = 0.0);
+    // K / D per camera, pinhole or equidistant (:62-94): dist = true, the tracked intrinsics are Pl's
+    PinholeStereoCamera(int width, int height, double b, const double Kl[4], const double Kr[4],
+                        const double Rl[9], const double Rr[9], const double Pl[4], const double Pr[4],
+                        const std::vector<double>& Dl, const std::vector<double>& Dr, bool equi);
     // a copy is a new camera: it gets its own frame engine (StereoFrame's frame-level members)
-    PinholeStereoCamera(const PinholeStereoCamera& o) : cam_(o.cam_) {}
+    // and its own rectifier
+    PinholeStereoCamera(const PinholeStereoCamera& o) : cam_(o.cam_), dist_(o.dist_) {
+        side_[0] = o.side_[0];
+        side_[1] = o.side_[1];
+    }
     PinholeStereoCamera& operator=(const PinholeStereoCamera& o) {
-        if (this != &o) { cam_ = o.cam_; engine_.reset(); }
+        if (this != &o) {
+            cam_ = o.cam_; dist_ = o.dist_; side_[0] = o.side_[0]; side_[1] = o.side_[1];
+            engine_.reset(); dropRectifier();
+        }
         return *this;
     }
     ~PinholeStereoCamera();
+    // rectifyImage / rectifyImagesLR (src/pinholeStereoCamera.cpp:98-119) on HOST grey images of
+    // width x height bytes (img_rec is resized); dist == false clones the input.  rectifyImage
+    // uses the left maps, as the reference does.
+    void rectifyImage(const std::vector<uint8_t>& img_src, std::vector<uint8_t>& img_rec) const;
+    void rectifyImagesLR(const std::vector<uint8_t>& img_src_l, std::vector<uint8_t>& img_rec_l,
+                         const std::vector<uint8_t>& img_src_r, std::vector<uint8_t>& img_rec_r) const;
+    // the same on DEVICE images, n per side ([n][height][width] u8, src != rec); synchronises.
+    // dist == false is an error here (GFPL_E_STATE): there is nothing to do but a device copy.
+    void rectifyImage(const uint8_t* dev_src, uint8_t* dev_rec, int n) const;
+    void rectifyImagesLR(const uint8_t* dev_src_l, uint8_t* dev_rec_l, const uint8_t* dev_src_r, uint8_t* dev_rec_r,
+                         int n) const;
+    bool distorted() const { return dist_; }
     int getWidth() const { return cam_.width; }
     int getHeight() const { return cam_.height; }
     double getFx() const { return cam_.fx; }
@@ -199,6 +241,15 @@ private:
     // created on first use and destroyed with the camera (not in a static destructor)
     mutable std::unique_ptr<StereoFrameHandler> engine_;
     mutable std::mutex engine_mu_;
+    // the distortion path: both cameras' parameters, and the device rectifier on a context of
+    // its own, created on first use
+    bool dist_ = false;
+    gfpl_rectify_side side_[2] = {};
+    mutable gfpl_ctx* rect_ctx_ = nullptr;
+    mutable gfpl_rectifier* rect_ = nullptr;
+    mutable std::mutex rect_mu_;
+    gfpl_rectifier* rectifier() const;
+    void dropRectifier();
 };
 
 // -------------------------------------------------------------- features --

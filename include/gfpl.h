@@ -49,6 +49,7 @@ extern "C" {
 #define GFPL_E_CAPACITY         (-5)   /* counts exceed the seqbatch capacity    */
 #define GFPL_E_STATE            (-6)   /* call order violated (e.g. insert before initialize) */
 #define GFPL_E_UNSUPPORTED      (-7)   /* config flag combination not on the path */
+#define GFPL_E_NOMEM            (-8)   /* device memory allocation failed        */
 
 /* which frame of a sequence */
 #define GFPL_PREV 0
@@ -571,6 +572,52 @@ typedef struct gfpl_detections_host {
     uint8_t* ldesc_l;     uint8_t* ldesc_r;   /* [cap][32] */
 } gfpl_detections_host;
 int  gfpl_read_detections(gfpl_ctx* ctx, const gfpl_frames* view, int seq, gfpl_detections_host* out);
+
+/* ------------------------------------------- stereo rectification (§4f) ---- */
+/* PinholeStereoCamera's distortion path (src/pinholeStereoCamera.cpp:24-119): the
+ * constructor's initUndistortRectifyMap(K, D, R, P, size, CV_16SC2, map1, map2) (or the
+ * cv::fisheye one for the equidistant model) per camera, and rectifyImage's
+ * cv::remap(src, dst, map1, map2, INTER_LINEAR) per frame, as app/plslam_mod.cpp:348-351
+ * runs it on every stereo pair before the tracker sees it.  8-bit single-channel images,
+ * BORDER_CONSTANT 0.  R and P are the caller's (cv::stereoRectify is not part of this).
+ * Arithmetic pinned as ledger R1-R6.                                    */
+typedef struct gfpl_rectify_side {   /* one camera of the rig */
+    int    model;        /* 0 = pinhole radial-tangential, 1 = equidistant (fisheye) */
+    double K[4];         /* fx fy cx cy of the raw camera                            */
+    double D[8]; int n_dist;  /* pinhole: k1 k2 p1 p2 [k3 [k4 k5 k6]] (4, 5 or 8); fisheye: k1..k4 (4) */
+    double R[9];         /* rectifying rotation, row-major                            */
+    double P[4];         /* fx fy cx cy of the rectified camera (left 3x3 of P)      */
+} gfpl_rectify_side;
+/* The maps of one camera on the HOST (no device needed): map1 [H][W][2] (x, y) the integer
+ * source position, map2 [H][W] the 5 + 5 fractional bits (CV_16SC2 + CV_16UC1).  1..8192 px.
+ * GFPL_E_UNSUPPORTED for another coefficient count (thin-prism / tilt terms), GFPL_E_INVALID
+ * for another model, a NULL pointer or a singular P R.                                     */
+int  gfpl_rectify_maps_host(const gfpl_rectify_side* s, int width, int height,
+                            int16_t* map1 /*[H][W][2] x,y*/, uint16_t* map2 /*[H][W]*/);
+typedef struct gfpl_rectifier gfpl_rectifier;
+/* builds both cameras' maps and uploads them; images of width x height (8..8192 px).  The
+ * context cannot be destroyed while the rectifier lives.  GFPL_E_NOMEM when the device
+ * allocation fails.                                                                        */
+int  gfpl_rectifier_create(gfpl_ctx* ctx, const gfpl_rectify_side* left, const gfpl_rectify_side* right,
+                           int width, int height, gfpl_rectifier** out);
+int  gfpl_rectifier_destroy(gfpl_rectifier* r);
+/* the uploaded maps of side 0 (left) / 1 (right), read back into HOST arrays; synchronises */
+int  gfpl_rectifier_read_maps(gfpl_rectifier* r, int side, int16_t* map1, uint16_t* map2);
+/* rectifyImage for n images of one side: src / dst DEVICE u8 [n][H][W], side 0 / 1; the two
+ * ranges must not overlap (GFPL_E_INVALID).  gfpl_rectify synchronises; the _async forms are
+ * enqueued on the context's stream.  gfpl_rectify_stereo_async is rectifyImagesLR: both sides
+ * of n stereo frames in one launch.                                                        */
+int  gfpl_rectify(gfpl_rectifier* r, int side, const uint8_t* src, int n, uint8_t* dst);
+int  gfpl_rectify_async(gfpl_rectifier* r, int side, const uint8_t* src, int n, uint8_t* dst);
+int  gfpl_rectify_stereo_async(gfpl_rectifier* r, const uint8_t* src_l, const uint8_t* src_r, int n,
+                               uint8_t* dst_l, uint8_t* dst_r);
+/* the same from / to HOST images (staged in device memory the rectifier keeps); synchronises */
+int  gfpl_rectify_host(gfpl_rectifier* r, int side, const uint8_t* src, int n, uint8_t* dst);
+/* Raw images in: with a rectifier attached, gfpl_detect_stereo_async / _host rectify their
+ * inputs into the detector's own buffer set instead of copying them (the caller may still
+ * overwrite its inputs after the call returns).  The rectifier's image size must be the
+ * detector's camera's (GFPL_E_INVALID) and it must outlive the attachment; NULL detaches. */
+int  gfpl_detector_set_rectifier(gfpl_detector* det, gfpl_rectifier* r);
 
 /* ------------------------------------------------- keyframe consumers ---- */
 /* One keyframe's stereo features as KeyFrame::stereo_frame exposes them
