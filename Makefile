@@ -21,7 +21,7 @@ HIP_HDR  := $(wildcard $(PKG)/csrc/*.hpp) include/gfpl.h
 BINDIR   := $(PKG)/bin
 
 all: $(LIBDIR)/libgfpl_hip.so $(LIBDIR)/libgfpl_synth.so oracle/liboracle.so $(LIBDIR)/libgfpl_stvo.so $(BINDIR)/plslam_gpu \
-     $(BINDIR)/mirror_maphandler $(BINDIR)/mirror_rectify
+     $(BINDIR)/mirror_maphandler $(BINDIR)/mirror_rectify $(BINDIR)/layout_check
 
 $(LIBDIR)/libgfpl_hip.so: $(HIP_SRC) $(HIP_HDR)
 	@mkdir -p $(LIBDIR)
@@ -53,6 +53,19 @@ $(BINDIR)/mirror_rectify: tests/mirror_rectify.cpp $(LIBDIR)/libgfpl_stvo.so
 	$(CXX) -O2 -std=c++17 -ffp-contract=off -Wall -Iinclude $< -o $@ -L$(LIBDIR) -lgfpl_stvo -lgfpl_hip -lpthread \
 	    -Wl,-rpath,'$$ORIGIN/../lib'
 
+# every dynamic-LDS layout's offsets and bytes (tests/test_layouts.py): host code only, no HIP API
+LAYOUTFLAGS := -O1 -g -std=c++17 -x hip --cuda-host-only -Wall -Iinclude
+$(BINDIR)/layout_check: tests/layout_check.cpp $(PKG)/csrc/gfpl_layout.hpp include/gfpl.h
+	@mkdir -p $(BINDIR)
+	$(HIPCC) $(LAYOUTFLAGS) $< -o $@
+# the same under ASan + UBSan, over the project's image heights
+oracle/build/layout_check_asan: tests/layout_check.cpp $(PKG)/csrc/gfpl_layout.hpp include/gfpl.h
+	@mkdir -p oracle/build
+	$(HIPCC) $(LAYOUTFLAGS) -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all $< -o $@
+layout-asan: oracle/build/layout_check_asan
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 \
+	    ./oracle/build/layout_check_asan 480:4 480:8 376:4 376:8 1080:4 1080:8 > /dev/null
+
 ORACLE_SRC := oracle/gfpl_oracle.cpp oracle/gfpl_orb_oracle.cpp oracle/gfpl_lbd_oracle.cpp oracle/gfpl_lsd_oracle.cpp
 oracle/liboracle.so: $(ORACLE_SRC) oracle/gfpl_oracle.h include/gfpl.h $(PKG)/csrc/gfpl_orb_pattern.h
 	$(CXX) $(ORACLEFLAGS) $(ORACLE_SRC) -o $@
@@ -75,6 +88,7 @@ hip: $(LIBDIR)/libgfpl_hip.so
 host: $(LIBDIR)/libgfpl_stvo.so $(BINDIR)/plslam_gpu $(BINDIR)/mirror_maphandler $(BINDIR)/mirror_rectify
 
 clean:
-	rm -f $(LIBDIR)/*.so oracle/liboracle.so $(BINDIR)/plslam_gpu $(BINDIR)/mirror_maphandler $(BINDIR)/mirror_rectify oracle/build/asan_driver
+	rm -f $(LIBDIR)/*.so oracle/liboracle.so $(BINDIR)/plslam_gpu $(BINDIR)/mirror_maphandler $(BINDIR)/mirror_rectify $(BINDIR)/layout_check \
+	    oracle/build/asan_driver oracle/build/layout_check_asan
 
-.PHONY: all clean oracle oracle-asan synth hip host
+.PHONY: all clean oracle oracle-asan layout-asan synth hip host

@@ -90,48 +90,53 @@ namespace {
         }                                                           \
     } while (0)
 
-// bump allocator over one device allocation (256-B aligned fields)
-struct Carver {
-    size_t off = 0;
-    char* base = nullptr;
-    template <typename T>
-    T* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += n * sizeof(T);
-        return p;
-    }
-};
-
 int debug_fill_byte() {
     const char* e = getenv("GFPL_DEBUG_FILL");
     return e ? (int)(strtol(e, nullptr, 0) & 0xFF) : 0;
 }
 
+// Every field of a frame slot, once, in layout order: device member, host member
+// (gfpl_frame_host) and elements per feature.  v.pt / v.ls: a row per point / per line;
+// v.count: a list's length [B]; v.seq: per sequence.  Drives carve(), gfpl_read_frame
+// and gfpl_write_frame.
+template <typename F, typename H, typename V>
+void frame_fields(F& f, H& o, V& v) {
+    v.pt(f.pt.pl, o.pt_pl, 2); v.pt(f.pt.pl_obs, o.pt_pl_obs, 2);
+    v.pt(f.pt.disp, o.pt_disp, 1); v.pt(f.pt.P, o.pt_P, 3); v.pt(f.pt.sigma2, o.pt_sigma2, 1);
+    v.pt(f.pt.idx, o.pt_idx, 1); v.pt(f.pt.level, o.pt_level, 1); v.pt(f.pt.inlier, o.pt_inlier, 1);
+    v.pt(f.pt.desc, o.pdesc, 32); v.count(f.pt.n);
+    v.ls(f.ls.spl, o.ls_spl, 2); v.ls(f.ls.epl, o.ls_epl, 2);
+    v.ls(f.ls.spl_obs, o.ls_spl_obs, 2); v.ls(f.ls.epl_obs, o.ls_epl_obs, 2);
+    v.ls(f.ls.sdisp, o.ls_sdisp, 1); v.ls(f.ls.edisp, o.ls_edisp, 1);
+    v.ls(f.ls.sdisp_obs, o.ls_sdisp_obs, 1); v.ls(f.ls.edisp_obs, o.ls_edisp_obs, 1);
+    v.ls(f.ls.angle, o.ls_angle, 1); v.ls(f.ls.sigma2, o.ls_sigma2, 1);
+    v.ls(f.ls.sP, o.ls_sP, 3); v.ls(f.ls.eP, o.ls_eP, 3);
+    v.ls(f.ls.le, o.ls_le, 3); v.ls(f.ls.le_obs, o.ls_le_obs, 3);
+    v.ls(f.ls.covS, o.ls_covS, 9); v.ls(f.ls.covE, o.ls_covE, 9);
+    v.ls(f.ls.cut, o.ls_cut, 2); v.ls(f.ls.invcov, o.ls_invcov, 36);
+    v.ls(f.ls.idx, o.ls_idx, 1); v.ls(f.ls.level, o.ls_level, 1); v.ls(f.ls.inlier, o.ls_inlier, 1);
+    v.ls(f.ls.desc, o.ldesc, 32); v.count(f.ls.n);
+    v.seq(f.pose.Tfw, o.Tfw, 16); v.seq(f.pose.DT, o.DT, 16);
+    v.seq(f.pose.DT_cov, o.DT_cov, 36); v.seq(f.pose.Tfw_cov, o.Tfw_cov, 36);
+    v.seq(f.pose.DT_cov_eig, o.DT_cov_eig, 6);
+    v.seq(f.pose.err_norm, &o.err_norm, 1); v.seq(f.pose.time_stamp, &o.time_stamp, 1);
+}
+
+// carve(): every field at the seqbatch's full capacity
+struct SlotCarve {
+    Carver& c;
+    size_t B, P, L;
+    template <typename T, typename U> void pt(T*& d, U, int w) { d = c.take<T>(P * w); }
+    template <typename T, typename U> void ls(T*& d, U, int w) { d = c.take<T>(L * w); }
+    template <typename T, typename U> void seq(T*& d, U, int w) { d = c.take<T>(B * w); }
+    void count(int32_t*& d) { d = c.take<int32_t>(B); }
+};
+
 void carve(Carver& c, gfpl_seqbatch* sb) {
     const size_t B = sb->B, P = (size_t)B * sb->kp_cap, L = (size_t)B * sb->kl_cap;
-    for (int s = 0; s < 2; ++s) {
-        DevFrame& f = sb->slot[s];
-        f.pt.pl = c.take<double>(P * 2); f.pt.pl_obs = c.take<double>(P * 2);
-        f.pt.disp = c.take<double>(P); f.pt.P = c.take<double>(P * 3); f.pt.sigma2 = c.take<double>(P);
-        f.pt.idx = c.take<int32_t>(P); f.pt.level = c.take<int32_t>(P); f.pt.inlier = c.take<uint8_t>(P);
-        f.pt.desc = c.take<uint8_t>(P * 32); f.pt.n = c.take<int32_t>(B);
-        f.ls.spl = c.take<double>(L * 2); f.ls.epl = c.take<double>(L * 2);
-        f.ls.spl_obs = c.take<double>(L * 2); f.ls.epl_obs = c.take<double>(L * 2);
-        f.ls.sdisp = c.take<double>(L); f.ls.edisp = c.take<double>(L);
-        f.ls.sdisp_obs = c.take<double>(L); f.ls.edisp_obs = c.take<double>(L);
-        f.ls.angle = c.take<double>(L); f.ls.sigma2 = c.take<double>(L);
-        f.ls.sP = c.take<double>(L * 3); f.ls.eP = c.take<double>(L * 3);
-        f.ls.le = c.take<double>(L * 3); f.ls.le_obs = c.take<double>(L * 3);
-        f.ls.covS = c.take<double>(L * 9); f.ls.covE = c.take<double>(L * 9);
-        f.ls.cut = c.take<double>(L * 2); f.ls.invcov = c.take<double>(L * 36);
-        f.ls.idx = c.take<int32_t>(L); f.ls.level = c.take<int32_t>(L); f.ls.inlier = c.take<uint8_t>(L);
-        f.ls.desc = c.take<uint8_t>(L * 32); f.ls.n = c.take<int32_t>(B);
-        f.pose.Tfw = c.take<double>(B * 16); f.pose.DT = c.take<double>(B * 16);
-        f.pose.DT_cov = c.take<double>(B * 36); f.pose.Tfw_cov = c.take<double>(B * 36);
-        f.pose.DT_cov_eig = c.take<double>(B * 6);
-        f.pose.err_norm = c.take<double>(B); f.pose.time_stamp = c.take<double>(B);
-    }
+    const gfpl_frame_host none{};
+    SlotCarve v{c, B, P, L};
+    for (int s = 0; s < 2; ++s) frame_fields(sb->slot[s], none, v);
     sb->tr.matched_pt = c.take<int32_t>(B * sb->mpt_cap);
     sb->tr.n_matched_pt = c.take<int32_t>(B);
     sb->tr.matched_ls = c.take<int32_t>(B * sb->mls_cap);
@@ -1104,11 +1109,47 @@ hipError_t h2d(T* dst, const T* src, size_t n, hipStream_t s) {
     if (!src || n == 0) return hipSuccess;
     return hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, s);
 }
+#define XFER(fn, a, b, n) HIPCHK(fn(a, b, n, s))
+
+// one sequence's rows of every frame field, device -> host (READ) or host -> device; the list
+// lengths travel on their own (first, in both directions); the first failing copy ends the rest
+template <bool READ>
+struct SlotCopy {
+    hipStream_t s;
+    size_t b, P, L, np, nl;   // the sequence, its first point / line row, its list lengths
+    hipError_t e = hipSuccess;
+    template <typename T, typename U>
+    void rows(T* d, U* h, size_t off, size_t n) {
+        if (e != hipSuccess) return;
+        if constexpr (READ) e = d2h(h, d + off, n, s);
+        else e = h2d(d + off, h, n, s);
+    }
+    template <typename T, typename U> void pt(T* d, U* h, int w) { rows(d, h, w * P, w * np); }
+    template <typename T, typename U> void ls(T* d, U* h, int w) { rows(d, h, w * L, w * nl); }
+    template <typename T, typename U> void seq(T* d, U* h, int w) { rows(d, h, w * b, (size_t)w); }
+    void count(int32_t*) {}
+};
+
+int read_track(gfpl_seqbatch* sb, int seq, gfpl_track_host* o, const int32_t* n_pt, const int32_t* n_ls) {
+    if (!sb || !o || seq < 0 || seq >= sb->B) return GFPL_E_INVALID;
+    hipStream_t s = sb->ctx->stream;
+    HIPCHK(hipStreamSynchronize(s));
+    std::memset(o, 0, sizeof(*o));
+    XFER(d2h, &o->n_matched_pt, n_pt + seq, 1);
+    XFER(d2h, &o->n_matched_ls, n_ls + seq, 1);
+    XFER(d2h, &o->n_inliers, sb->tr.n_inliers + seq, 1);
+    XFER(d2h, &o->n_inliers_pt, sb->tr.n_inliers_pt + seq, 1);
+    XFER(d2h, &o->n_inliers_ls, sb->tr.n_inliers_ls + seq, 1);
+    XFER(d2h, &o->num_frame_loss, sb->tr.num_frame_loss + seq, 1);
+    HIPCHK(hipStreamSynchronize(s));
+    XFER(d2h, o->matched_pt, sb->tr.matched_pt + (size_t)seq * sb->mpt_cap, (size_t)o->n_matched_pt);
+    XFER(d2h, o->matched_ls, sb->tr.matched_ls + (size_t)seq * sb->mls_cap, (size_t)o->n_matched_ls);
+    HIPCHK(hipStreamSynchronize(s));
+    return GFPL_OK;
+}
 }  // namespace
 
 extern "C" {
-
-#define XFER(fn, a, b, n) HIPCHK(fn(a, b, n, s))
 
 int gfpl_read_frame(gfpl_seqbatch* sb, int which, int seq, gfpl_frame_host* o) {
     if (!sb || !o || seq < 0 || seq >= sb->B || (which != GFPL_PREV && which != GFPL_CURR)) return GFPL_E_INVALID;
@@ -1119,45 +1160,9 @@ int gfpl_read_frame(gfpl_seqbatch* sb, int which, int seq, gfpl_frame_host* o) {
     HIPCHK(hipMemcpy(&np, f.pt.n + seq, 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(&nl, f.ls.n + seq, 4, hipMemcpyDeviceToHost));
     o->n_pt = np; o->n_ls = nl;
-    const size_t P = (size_t)seq * sb->kp_cap, L = (size_t)seq * sb->kl_cap;
-    XFER(d2h, o->pt_pl, f.pt.pl + 2 * P, 2 * (size_t)np);
-    XFER(d2h, o->pt_pl_obs, f.pt.pl_obs + 2 * P, 2 * (size_t)np);
-    XFER(d2h, o->pt_disp, f.pt.disp + P, (size_t)np);
-    XFER(d2h, o->pt_P, f.pt.P + 3 * P, 3 * (size_t)np);
-    XFER(d2h, o->pt_sigma2, f.pt.sigma2 + P, (size_t)np);
-    XFER(d2h, o->pt_idx, f.pt.idx + P, (size_t)np);
-    XFER(d2h, o->pt_level, f.pt.level + P, (size_t)np);
-    XFER(d2h, o->pt_inlier, f.pt.inlier + P, (size_t)np);
-    XFER(d2h, o->pdesc, f.pt.desc + 32 * P, 32 * (size_t)np);
-    XFER(d2h, o->ls_spl, f.ls.spl + 2 * L, 2 * (size_t)nl);
-    XFER(d2h, o->ls_epl, f.ls.epl + 2 * L, 2 * (size_t)nl);
-    XFER(d2h, o->ls_spl_obs, f.ls.spl_obs + 2 * L, 2 * (size_t)nl);
-    XFER(d2h, o->ls_epl_obs, f.ls.epl_obs + 2 * L, 2 * (size_t)nl);
-    XFER(d2h, o->ls_sdisp, f.ls.sdisp + L, (size_t)nl);
-    XFER(d2h, o->ls_edisp, f.ls.edisp + L, (size_t)nl);
-    XFER(d2h, o->ls_sdisp_obs, f.ls.sdisp_obs + L, (size_t)nl);
-    XFER(d2h, o->ls_edisp_obs, f.ls.edisp_obs + L, (size_t)nl);
-    XFER(d2h, o->ls_angle, f.ls.angle + L, (size_t)nl);
-    XFER(d2h, o->ls_sigma2, f.ls.sigma2 + L, (size_t)nl);
-    XFER(d2h, o->ls_sP, f.ls.sP + 3 * L, 3 * (size_t)nl);
-    XFER(d2h, o->ls_eP, f.ls.eP + 3 * L, 3 * (size_t)nl);
-    XFER(d2h, o->ls_le, f.ls.le + 3 * L, 3 * (size_t)nl);
-    XFER(d2h, o->ls_le_obs, f.ls.le_obs + 3 * L, 3 * (size_t)nl);
-    XFER(d2h, o->ls_covS, f.ls.covS + 9 * L, 9 * (size_t)nl);
-    XFER(d2h, o->ls_covE, f.ls.covE + 9 * L, 9 * (size_t)nl);
-    XFER(d2h, o->ls_cut, f.ls.cut + 2 * L, 2 * (size_t)nl);
-    XFER(d2h, o->ls_invcov, f.ls.invcov + 36 * L, 36 * (size_t)nl);
-    XFER(d2h, o->ls_idx, f.ls.idx + L, (size_t)nl);
-    XFER(d2h, o->ls_level, f.ls.level + L, (size_t)nl);
-    XFER(d2h, o->ls_inlier, f.ls.inlier + L, (size_t)nl);
-    XFER(d2h, o->ldesc, f.ls.desc + 32 * L, 32 * (size_t)nl);
-    XFER(d2h, o->Tfw, f.pose.Tfw + 16 * seq, 16);
-    XFER(d2h, o->DT, f.pose.DT + 16 * seq, 16);
-    XFER(d2h, o->DT_cov, f.pose.DT_cov + 36 * seq, 36);
-    XFER(d2h, o->Tfw_cov, f.pose.Tfw_cov + 36 * seq, 36);
-    XFER(d2h, o->DT_cov_eig, f.pose.DT_cov_eig + 6 * seq, 6);
-    XFER(d2h, &o->err_norm, f.pose.err_norm + seq, 1);
-    XFER(d2h, &o->time_stamp, f.pose.time_stamp + seq, 1);
+    SlotCopy<true> v{s, (size_t)seq, (size_t)seq * sb->kp_cap, (size_t)seq * sb->kl_cap, (size_t)np, (size_t)nl};
+    frame_fields(f, *o, v);
+    HIPCHK(v.e);
     HIPCHK(hipStreamSynchronize(s));
     return GFPL_OK;
 }
@@ -1166,49 +1171,12 @@ int gfpl_write_frame(gfpl_seqbatch* sb, int which, int seq, const gfpl_frame_hos
     if (!sb || !o || seq < 0 || seq >= sb->B || (which != GFPL_PREV && which != GFPL_CURR)) return GFPL_E_INVALID;
     if (o->n_pt < 0 || o->n_pt > sb->kp_cap || o->n_ls < 0 || o->n_ls > sb->kl_cap) return GFPL_E_CAPACITY;
     hipStream_t s = sb->ctx->stream;
-    DevFrame& f = sb->slot[which == GFPL_PREV ? sb->prev_slot : 1 - sb->prev_slot];
-    const int np = o->n_pt, nl = o->n_ls;
-    const size_t P = (size_t)seq * sb->kp_cap, L = (size_t)seq * sb->kl_cap;
+    const DevFrame& f = sb->slot[which == GFPL_PREV ? sb->prev_slot : 1 - sb->prev_slot];
     XFER(h2d, f.pt.n + seq, &o->n_pt, 1);
     XFER(h2d, f.ls.n + seq, &o->n_ls, 1);
-    XFER(h2d, f.pt.pl + 2 * P, o->pt_pl, 2 * (size_t)np);
-    XFER(h2d, f.pt.pl_obs + 2 * P, o->pt_pl_obs, 2 * (size_t)np);
-    XFER(h2d, f.pt.disp + P, o->pt_disp, (size_t)np);
-    XFER(h2d, f.pt.P + 3 * P, o->pt_P, 3 * (size_t)np);
-    XFER(h2d, f.pt.sigma2 + P, o->pt_sigma2, (size_t)np);
-    XFER(h2d, f.pt.idx + P, o->pt_idx, (size_t)np);
-    XFER(h2d, f.pt.level + P, o->pt_level, (size_t)np);
-    XFER(h2d, f.pt.inlier + P, o->pt_inlier, (size_t)np);
-    XFER(h2d, f.pt.desc + 32 * P, o->pdesc, 32 * (size_t)np);
-    XFER(h2d, f.ls.spl + 2 * L, o->ls_spl, 2 * (size_t)nl);
-    XFER(h2d, f.ls.epl + 2 * L, o->ls_epl, 2 * (size_t)nl);
-    XFER(h2d, f.ls.spl_obs + 2 * L, o->ls_spl_obs, 2 * (size_t)nl);
-    XFER(h2d, f.ls.epl_obs + 2 * L, o->ls_epl_obs, 2 * (size_t)nl);
-    XFER(h2d, f.ls.sdisp + L, o->ls_sdisp, (size_t)nl);
-    XFER(h2d, f.ls.edisp + L, o->ls_edisp, (size_t)nl);
-    XFER(h2d, f.ls.sdisp_obs + L, o->ls_sdisp_obs, (size_t)nl);
-    XFER(h2d, f.ls.edisp_obs + L, o->ls_edisp_obs, (size_t)nl);
-    XFER(h2d, f.ls.angle + L, o->ls_angle, (size_t)nl);
-    XFER(h2d, f.ls.sigma2 + L, o->ls_sigma2, (size_t)nl);
-    XFER(h2d, f.ls.sP + 3 * L, o->ls_sP, 3 * (size_t)nl);
-    XFER(h2d, f.ls.eP + 3 * L, o->ls_eP, 3 * (size_t)nl);
-    XFER(h2d, f.ls.le + 3 * L, o->ls_le, 3 * (size_t)nl);
-    XFER(h2d, f.ls.le_obs + 3 * L, o->ls_le_obs, 3 * (size_t)nl);
-    XFER(h2d, f.ls.covS + 9 * L, o->ls_covS, 9 * (size_t)nl);
-    XFER(h2d, f.ls.covE + 9 * L, o->ls_covE, 9 * (size_t)nl);
-    XFER(h2d, f.ls.cut + 2 * L, o->ls_cut, 2 * (size_t)nl);
-    XFER(h2d, f.ls.invcov + 36 * L, o->ls_invcov, 36 * (size_t)nl);
-    XFER(h2d, f.ls.idx + L, o->ls_idx, (size_t)nl);
-    XFER(h2d, f.ls.level + L, o->ls_level, (size_t)nl);
-    XFER(h2d, f.ls.inlier + L, o->ls_inlier, (size_t)nl);
-    XFER(h2d, f.ls.desc + 32 * L, o->ldesc, 32 * (size_t)nl);
-    XFER(h2d, f.pose.Tfw + 16 * seq, o->Tfw, 16);
-    XFER(h2d, f.pose.DT + 16 * seq, o->DT, 16);
-    XFER(h2d, f.pose.DT_cov + 36 * seq, o->DT_cov, 36);
-    XFER(h2d, f.pose.Tfw_cov + 36 * seq, o->Tfw_cov, 36);
-    XFER(h2d, f.pose.DT_cov_eig + 6 * seq, o->DT_cov_eig, 6);
-    XFER(h2d, f.pose.err_norm + seq, &o->err_norm, 1);
-    XFER(h2d, f.pose.time_stamp + seq, &o->time_stamp, 1);
+    SlotCopy<false> v{s, (size_t)seq, (size_t)seq * sb->kp_cap, (size_t)seq * sb->kl_cap, (size_t)o->n_pt, (size_t)o->n_ls};
+    frame_fields(f, *o, v);
+    HIPCHK(v.e);
     HIPCHK(hipStreamSynchronize(s));
     sb->initialized = true;
     if (which == GFPL_CURR) sb->has_curr = true;
@@ -1216,39 +1184,12 @@ int gfpl_write_frame(gfpl_seqbatch* sb, int which, int seq, const gfpl_frame_hos
 }
 
 int gfpl_read_track(gfpl_seqbatch* sb, int seq, gfpl_track_host* o) {
-    if (!sb || !o || seq < 0 || seq >= sb->B) return GFPL_E_INVALID;
-    hipStream_t s = sb->ctx->stream;
-    HIPCHK(hipStreamSynchronize(s));
-    std::memset(o, 0, sizeof(*o));
-    XFER(d2h, &o->n_matched_pt, sb->tr.n_matched_pt + seq, 1);
-    XFER(d2h, &o->n_matched_ls, sb->tr.n_matched_ls + seq, 1);
-    XFER(d2h, &o->n_inliers, sb->tr.n_inliers + seq, 1);
-    XFER(d2h, &o->n_inliers_pt, sb->tr.n_inliers_pt + seq, 1);
-    XFER(d2h, &o->n_inliers_ls, sb->tr.n_inliers_ls + seq, 1);
-    XFER(d2h, &o->num_frame_loss, sb->tr.num_frame_loss + seq, 1);
-    HIPCHK(hipStreamSynchronize(s));
-    XFER(d2h, o->matched_pt, sb->tr.matched_pt + (size_t)seq * sb->mpt_cap, (size_t)o->n_matched_pt);
-    XFER(d2h, o->matched_ls, sb->tr.matched_ls + (size_t)seq * sb->mls_cap, (size_t)o->n_matched_ls);
-    HIPCHK(hipStreamSynchronize(s));
-    return GFPL_OK;
+    return read_track(sb, seq, o, sb ? sb->tr.n_matched_pt : nullptr, sb ? sb->tr.n_matched_ls : nullptr);
 }
 
+// the lists as they were before the last gfpl_update_frame cleared their lengths
 int gfpl_read_last_track(gfpl_seqbatch* sb, int seq, gfpl_track_host* o) {
-    if (!sb || !o || seq < 0 || seq >= sb->B) return GFPL_E_INVALID;
-    hipStream_t s = sb->ctx->stream;
-    HIPCHK(hipStreamSynchronize(s));
-    std::memset(o, 0, sizeof(*o));
-    XFER(d2h, &o->n_matched_pt, sb->last_n_pt + seq, 1);
-    XFER(d2h, &o->n_matched_ls, sb->last_n_ls + seq, 1);
-    XFER(d2h, &o->n_inliers, sb->tr.n_inliers + seq, 1);
-    XFER(d2h, &o->n_inliers_pt, sb->tr.n_inliers_pt + seq, 1);
-    XFER(d2h, &o->n_inliers_ls, sb->tr.n_inliers_ls + seq, 1);
-    XFER(d2h, &o->num_frame_loss, sb->tr.num_frame_loss + seq, 1);
-    HIPCHK(hipStreamSynchronize(s));
-    XFER(d2h, o->matched_pt, sb->tr.matched_pt + (size_t)seq * sb->mpt_cap, (size_t)o->n_matched_pt);
-    XFER(d2h, o->matched_ls, sb->tr.matched_ls + (size_t)seq * sb->mls_cap, (size_t)o->n_matched_ls);
-    HIPCHK(hipStreamSynchronize(s));
-    return GFPL_OK;
+    return read_track(sb, seq, o, sb ? sb->last_n_pt : nullptr, sb ? sb->last_n_ls : nullptr);
 }
 
 int gfpl_write_track(gfpl_seqbatch* sb, int seq, const gfpl_track_host* o) {

@@ -230,33 +230,33 @@ int gfpl_detector_create(gfpl_ctx* ctx, const gfpl_detector_params* prm, int max
         for (gfpl_event** ev : {&d->set[s].ready, &d->set[s].orb_done, &d->set[s].copied, &d->set[s].consumed})
             if (!e) e = gfpl_event_create(ctx, ev);
     if (e) { teardown(d); return e; }
-    // one allocation for every set, 256-B aligned fields
-    const size_t B = max_batch, img = (size_t)d->W * d->H;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t per_set = al(2 * B * img) + 2 * al(4 * B) + 2 * al(B * kp_cap * sizeof(gfpl_keypoint)) +
-                           2 * al(B * kp_cap * 32) + al(8 * B) + al(2 * B * kl_cap * sizeof(gfpl_keyline)) +
-                           2 * al(B * kl_cap * 32) + 2 * al(B * (size_t)d->pyr_bytes) + al(8 * B);
-    if (hipSetDevice(dev) != hipSuccess || hipMalloc(&d->base, per_set * sets) != hipSuccess ||
-        hipMemset(d->base, 0, per_set * sets) != hipSuccess) {
+    // one allocation for every set
+    auto layout = [&](gfpl::Carver& c) {
+        const size_t B = max_batch, img = (size_t)d->W * d->H;
+        for (int s = 0; s < sets; ++s) {
+            DetSet& S = d->set[s];
+            S.img = c.take<uint8_t>(2 * B * img);
+            for (int side = 0; side < 2; ++side) {
+                S.n_kp[side] = c.take<int>(B);
+                S.kp[side] = c.take<gfpl_keypoint>(B * kp_cap);
+                S.pdesc[side] = c.take<uint8_t>(B * kp_cap * 32);
+            }
+            S.n_kl = c.take<int>(2 * B);
+            S.kl = c.take<gfpl_keyline>(2 * B * kl_cap);
+            for (int side = 0; side < 2; ++side) S.ldesc[side] = c.take<uint8_t>(B * kl_cap * 32);
+            for (int side = 0; side < 2; ++side) S.pyr[side] = c.take<uint8_t>(B * (size_t)d->pyr_bytes);
+            S.ts = c.take<double>(B);
+        }
+    };
+    gfpl::Carver c;
+    layout(c);   // sizing pass (base == nullptr)
+    if (hipSetDevice(dev) != hipSuccess || hipMalloc(&d->base, c.off) != hipSuccess ||
+        hipMemset(d->base, 0, c.off) != hipSuccess) {
         teardown(d);
         return GFPL_E_HIP;
     }
-    char* p = (char*)d->base;
-    auto take = [&](size_t bytes) { char* q = p; p += al(bytes); return q; };
-    for (int s = 0; s < sets; ++s) {
-        DetSet& S = d->set[s];
-        S.img = (uint8_t*)take(2 * B * img);
-        for (int side = 0; side < 2; ++side) {
-            S.n_kp[side] = (int*)take(4 * B);
-            S.kp[side] = (gfpl_keypoint*)take(B * kp_cap * sizeof(gfpl_keypoint));
-            S.pdesc[side] = (uint8_t*)take(B * kp_cap * 32);
-        }
-        S.n_kl = (int*)take(8 * B);
-        S.kl = (gfpl_keyline*)take(2 * B * kl_cap * sizeof(gfpl_keyline));
-        for (int side = 0; side < 2; ++side) S.ldesc[side] = (uint8_t*)take(B * kl_cap * 32);
-        for (int side = 0; side < 2; ++side) S.pyr[side] = (uint8_t*)take(B * (size_t)d->pyr_bytes);
-        S.ts = (double*)take(8 * B);
-    }
+    c = gfpl::Carver{0, (char*)d->base};
+    layout(c);
     *out = d;
     return GFPL_OK;
 }

@@ -1,5 +1,6 @@
 // gfpl_kernels.hpp — launchers implemented in the k_*.hip translation units.
 #pragma once
+#include "gfpl_layout.hpp"
 #include "gfpl_state.hpp"
 
 #include <atomic>
@@ -19,6 +20,9 @@ inline hipError_t ensure_dyn_lds(const void* fn, int bytes, std::atomic<unsigned
     if (e == hipSuccess && bit) done->fetch_or(bit, std::memory_order_acq_rel);
     return e;
 }
+
+// the ceiling every kernel whose layout can exceed 64 KB asks for: a CU's 160 KB less room for static LDS
+constexpr int DYN_LDS_CEILING = 160 * 1024 - 1024;
 
 // the batch size up to which the stereo and cross stages run 16 waves per sequence (k_stereo.hip)
 int sp_wide_max_b();
@@ -42,8 +46,6 @@ hipError_t launch_pose(const KParams& p, hipStream_t s, hipEvent_t mark /* or nu
 hipError_t launch_step_bytes(const KParams& p, hipStream_t s);
 hipError_t launch_need_kf(const KParams& p, hipStream_t s);
 hipError_t launch_curr_frame_is_kf(const KParams& p, const int32_t* mask /* device [B] */, hipStream_t s);
-
-size_t stereo_lines_lds(int cap);
 
 // lookForCommonMatches keyframe-pair gate (k_kf.hip); all pointers device
 struct KfGate {

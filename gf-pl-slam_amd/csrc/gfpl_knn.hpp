@@ -17,6 +17,7 @@
 // dot products are exact whatever the hardware's k permutation inside a step.
 #pragma once
 #include "gfpl_device.hpp"
+#include "gfpl_layout.hpp"
 #include <type_traits>
 
 // GFPL_KNN_FP4 1: the same GEMMs on v_mfma_scale_f32_32x32x64_f8f6f4 with FP4 (E2M1) operands.  The
@@ -25,9 +26,7 @@
 // the keys are bit-identical to the i8 form.  One instruction covers K = 64 in the cycles the i8 form
 // takes for K = 32, and a fragment is 4 bits per k: half the expansion-table bytes, half the query
 // fragment registers.  0: the i8 form (kept for the A/B).
-#ifndef GFPL_KNN_FP4
-#define GFPL_KNN_FP4 1
-#endif
+// (the default, 1, is set in gfpl_layout.hpp: the format sizes the expansion table)
 // FP4 accumulator start: every accumulator register starts at 1.5 * 2^23 (the first MFMA's C
 // operand): a float in [2^23, 2^24) has ulp 1, so its bit pattern is 0x4B400000 + count and the
 // key's `<< 16` drops the exponent bits with no extra instruction (no conversion to integer).
@@ -39,7 +38,6 @@ typedef int mfma_v8i __attribute__((ext_vector_type(8)));
 typedef int mfma_v16i __attribute__((ext_vector_type(16)));
 typedef float mfma_v16f __attribute__((ext_vector_type(16)));
 
-constexpr bool KNN_FP4 = GFPL_KNN_FP4 != 0;
 // k-steps (MFMAs) per tile: K = 512 (CELL 2) / 256 (CELL 1) in steps of 64 (FP4) or 32 (i8)
 template <int CELL>
 constexpr int knn_ksteps() { return (CELL == 2 ? 512 : 256) / (KNN_FP4 ? 64 : 32); }
@@ -151,13 +149,7 @@ __device__ __forceinline__ int popc8(const uint32_t* d) {
     return s;
 }
 
-// Expansion table for the train (A) side, filled once per workgroup in LDS, one entry per byte value:
-// i8 : CELL 2: 4 dwords of one-hot cells (16 i8); CELL 1: 2 dwords of bits (8 i8)
-// FP4: CELL 2: 2 dwords (16 nibbles);             CELL 1: 1 dword (8 nibbles)
-template <int CELL>
-constexpr int knn_lut_entry_dwords() { return (CELL == 2 ? 4 : 2) / (KNN_FP4 ? 2 : 1); }
-template <int CELL>
-constexpr int knn_lut_dwords() { return 256 * knn_lut_entry_dwords<CELL>(); }
+// Expansion table for the train (A) side, filled once per workgroup in LDS (knn_lut_dwords, gfpl_layout.hpp)
 template <int CELL>
 __device__ void knn_lut_fill(uint32_t* lut) {
     for (int b = threadIdx.x; b < 256; b += blockDim.x) {
@@ -439,7 +431,7 @@ __global__ void __launch_bounds__(256) k_knn2m(const uint8_t* q, const int* nq_a
     __shared__ __align__(16) uint32_t T[KNN_CHUNK * 8];
     // static LDS, so the table is not at LDS address 0: read through knn_frag_lut (lut-relative), never
     // through knn2_mfma<.., LUT0 = true>
-    __shared__ __align__(16) uint32_t lut[knn_lut_dwords<CELL>()];
+    __shared__ __align__(16) uint32_t lut[knn_lut_dwords(CELL)];
     constexpr int KS = knn_ksteps<CELL>();
     const int b = blockIdx.y;
     const int nq = nq_arr ? min(nq_arr[b], cap_clamp) : nq_fixed;

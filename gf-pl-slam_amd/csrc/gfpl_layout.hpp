@@ -1,0 +1,214 @@
+// gfpl_layout.hpp — every hand-laid-out buffer of the library, stated once.
+//
+// A layout is one function (or one struct's constructor), run to size and run to place: over a
+// null base it yields only the total, over the real base the same takes yield the fields, so the
+// size and the pointers cannot disagree.  Carver cuts one device allocation (HBM) into 256-B
+// aligned fields; LdsCarver cuts a kernel's dynamic LDS, in the kernel over `smem` and in its
+// launcher over null (`.bytes` is the launch's dynamic-LDS size).  Neither forms a pointer from a
+// null base.  No HIP API and no device-only type here: a plain host program can include this file
+// (tests/layout_check.cpp prints every layout).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#if defined(__HIP__) || defined(__CUDACC__)
+#define GFPL_HD __host__ __device__
+#else
+#define GFPL_HD
+#endif
+
+// GFPL_KNN_FP4 (gfpl_knn.hpp): the knn operands' number format sizes the expansion table
+#ifndef GFPL_KNN_FP4
+#define GFPL_KNN_FP4 1
+#endif
+
+namespace gfpl {
+
+// bump allocator over one device allocation (256-B aligned fields); base == nullptr: sizing pass
+struct Carver {
+    size_t off = 0;
+    char* base = nullptr;
+    template <typename T>
+    T* take(size_t n) {
+        off = (off + 255) & ~(size_t)255;
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += n * sizeof(T);
+        return p;
+    }
+};
+
+// the same over a kernel's dynamic LDS.  Fields are packed: only a take that names an alignment
+// rounds the offset (rounding every take left address arithmetic in the kernels that the plain
+// sums do not have), so a layout's order must keep every field naturally aligned; layout_check
+// verifies that for every shape it prints.
+struct LdsCarver {
+    unsigned char* base;
+    int off = 0;
+    GFPL_HD explicit LdsCarver(unsigned char* b) : base(b) {}
+    template <typename T>
+    GFPL_HD T* take(int n, int align = 0) {
+        if (align) off = (off + align - 1) & ~(align - 1);
+#ifdef __HIP_DEVICE_COMPILE__
+        T* p = reinterpret_cast<T*>(base + off);   // (a kernel's base is never null)
+#else
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+#endif
+        off += n * (int)sizeof(T);
+        return p;
+    }
+};
+
+// ---- constants the layouts share with their kernels
+constexpr int SP_CHUNK = 32;      // sorted right-keypoint entries per staged descriptor chunk (k_stereo_points, SEG)
+constexpr int SP_MINR_PAD = 32;   // minr bins span [-PAD, H + PAD) (k_stereo_points, SEG): every band is shorter
+constexpr int CH_STRIDE = 66;     // doubles per GN chunk row (k_pose)
+constexpr int LSD_RING = 256;     // region list entries mirrored in LDS (k_lsd_grow_*)
+constexpr bool KNN_FP4 = GFPL_KNN_FP4 != 0;
+// Expansion table for the train (A) side of the knn MFMA, one entry per byte value:
+// i8 : CELL 2: 4 dwords of one-hot cells (16 i8); CELL 1: 2 dwords of bits (8 i8)
+// FP4: CELL 2: 2 dwords (16 nibbles);             CELL 1: 1 dword (8 nibbles)
+GFPL_HD constexpr int knn_lut_entry_dwords(int cell) { return (cell == 2 ? 4 : 2) / (KNN_FP4 ? 2 : 1); }
+GFPL_HD constexpr int knn_lut_dwords(int cell) { return 256 * knn_lut_entry_dwords(cell); }
+
+// Every layout below is a struct whose members are the takes, in order (members initialise in
+// declaration order): pad_* are named slack the launch has always reserved, "= x" marks an alias.
+
+// ---- k_stereo_points<BLOCK, SEG>, BLOCK / 64 waves: right keypoints sorted by row band start with
+// their x / band height / octave beside the keys, left keypoints in row order, and a per-row
+// (SEG: per octave segment and minr bin) first-candidate table
+struct StereoPointsLds {
+    LdsCarver c;
+    int KP2, nbin, nrl;   // nbin: (SEG) minr bins per octave segment; nrl: rowlo entries
+    uint32_t* rkey = c.take<uint32_t>(KP2);    // sorted right keys
+    uint32_t* order = c.take<uint32_t>(KP2);   // left keypoints in processing order, then the sub-pixel jobs
+    uint32_t* pairs = c.take<uint32_t>(KP2);   // per left keypoint (bestDist, bestIdxR, window)
+    float* recx = c.take<float>(KP2);          // right x in sorted order
+    uint16_t* recm = c.take<uint16_t>(KP2);    // band height << 8 | octave
+    uint16_t* rowlo = c.take<uint16_t>((nrl + 1) & ~1);
+    int* misc = c.take<int>(32);   // counters, the scan's wave sums at +4, (SEG) band heights at 22 + segment
+    int stg_end;                   // (SEG) the launch reserves 16 B for the staging's alignment ...
+    uint32_t* stg;                 // (SEG) [waves][SP_CHUNK][8] per-wave staging of right descriptors, 16-B aligned
+    uint8_t* pad;                  // SEG: ... what the alignment left of them; else the launch's 64-int misc
+    int bytes = c.off;
+    float* depth = recx;           // = recx: mvDepth of the sub-pixel pass (the right x are dead after the band scan)
+    uint32_t* hr = reinterpret_cast<uint32_t*>(rowlo);   // = rowlo: (SEG) u16 bin counts, two per word; then
+    uint16_t* offr = rowlo;                              // = rowlo: (SEG) the bin offsets
+    uint32_t* hl = stg;                                  // = stg: (SEG) left row counts (u16) before the staging is live
+    uint16_t* offl = reinterpret_cast<uint16_t*>(stg);   // = stg: (SEG) the left row offsets
+    GFPL_HD StereoPointsLds(unsigned char* smem, int KP2, int height, int n_levels, bool seg, int waves)
+        : c(smem), KP2(KP2), nbin(height + 2 * SP_MINR_PAD), nrl(seg ? (n_levels + 1) * nbin + 1 : height),
+          stg_end(c.off + 16 + waves * SP_CHUNK * 32), stg(seg ? c.take<uint32_t>(waves * SP_CHUNK * 8, 16) : nullptr),
+          pad(c.take<uint8_t>(seg ? stg_end - c.off : 32 * 4)) {}
+};
+
+// ---- k_stereo_lines<CELL, INITIAL, BLOCK>, one layout for both cells.
+// THE KNN TABLE COMES FIRST: knn2_mfma<.., LUT0 = true> reads it at LDS address 0, so `lut` is the
+// first take and a kernel using this layout (or CrossLinesLds) declares no static __shared__.
+// Only the train rows sit in LDS (the query rows stream from HBM into registers).
+// (k_stereo_lines, k_cross_lines and k_pose still walk their pointers by hand, for the compiler's
+// sake: their launchers size the launch from these structs and tests/test_layouts.py pins the
+// structs to the kernels' walks)
+struct StereoLinesLds {
+    LdsCarver c;
+    int cap, cell;
+    uint32_t* lut = c.take<uint32_t>(knn_lut_dwords(cell));   // at LDS address 0
+    uint32_t* tb = c.take<uint32_t>(cap * 8);                 // train rows R (knn_stage_views)
+    int* lr_i = c.take<int>(cap);    // L->R best key, then index
+    int* lr_d0 = c.take<int>(cap);
+    int* lr_d1 = c.take<int>(cap);   // L->R second key, then distance
+    int* rl_i = c.take<int>(cap);    // R->L best key (atomicMin), then index
+    int* hist = c.take<int>(260);    // lineDescriptorMAD deviations
+    int* pad_a = c.take<int>(8);     // (the launch's 64-int misc block: pad_a .. scan)
+    double* th = c.take<double>(1);  // nn12_dist_th
+    int* pad_b = c.take<int>(6);
+    int* scan = c.take<int>(48);     // block_exclusive_scan's wave sums
+    uint32_t* pad_lut = c.take<uint32_t>(knn_lut_dwords(2) - knn_lut_dwords(cell));   // the launch sizes CELL 2's table for both
+    int bytes = c.off;
+    GFPL_HD StereoLinesLds(unsigned char* smem, int cap, int cell) : c(smem), cap(cap), cell(cell) {}
+};
+
+// ---- k_cross_lines<BLOCK>; the knn table first (see StereoLinesLds)
+struct CrossLinesLds {
+    LdsCarver c;
+    int cap;
+    uint32_t* lut = c.take<uint32_t>(knn_lut_dwords(1));   // at LDS address 0
+    uint32_t* tb = c.take<uint32_t>(cap * 8);              // train rows: curr (knn_stage_views)
+    int* i12 = c.take<int>(cap);
+    int* d012 = c.take<int>(cap);
+    int* d112 = c.take<int>(cap);
+    int* i21 = c.take<int>(cap);
+    int* h12 = c.take<int>(260);   // (d1 - d0) histogram; cleared together with h0
+    int* h0 = c.take<int>(260);    // d0 histogram
+    // block_exclusive_scan's wave sums; with 16 waves its total is a 17th int, the low word of
+    // th[0]: every thread has read th before the first scan's barrier
+    int* scan = c.take<int>(16);
+    double* th = c.take<double>(2);   // nn12 threshold, match budget distance
+    int* pad = c.take<int>(44);       // (the rest of the launch's 64-int misc block)
+    int bytes = c.off;
+    GFPL_HD CrossLinesLds(unsigned char* smem, int cap) : c(smem), cap(cap) {}
+};
+
+// ---- k_cross_points<XL>.  XL: the exact projections of the bucketed points in LDS too (bucket
+// order, beside their float copies), so a candidate that passes the float pre-filter reads them
+// from LDS instead of an L2 round trip ahead of its descriptor load; for capacities whose LDS
+// then leaves two workgroups per CU (kp_cap <= 2048)
+struct CrossPointsLds {
+    LdsCarver c;
+    int cap, ncell;
+    bool xl;
+    double* prevT = c.take<double>(16);
+    double* Tinv = c.take<double>(16);
+    double* spxy = xl ? c.take<double>(2 * cap, 16) : nullptr;   // (XL) [cap][2], 16-B aligned pairs
+    int* cnt = c.take<int>(ncell + 2);     // bucket counts (incl. the wild bucket)
+    int* start = c.take<int>(ncell + 2);
+    int* sq = c.take<int>(cap);
+    float* spx = c.take<float>(cap);
+    float* spy = c.take<float>(cap);
+    int* lastT = c.take<int>(cap);
+    int* misc = c.take<int>(64);
+    int bytes = c.off;
+    GFPL_HD CrossPointsLds(unsigned char* smem, int cap, int ncell, bool xl) : c(smem), cap(cap), ncell(ncell), xl(xl) {}
+};
+
+// ---- k_pose<W>: the GN chunk rows and the outlier residuals are never live together
+struct PoseLds {
+    // doubles shared by the chunk rows and the sort buffer
+    GFPL_HD static int region(int W, int NP2) { return W * 16 * CH_STRIDE > NP2 ? W * 16 * CH_STRIDE : NP2; }
+    LdsCarver c;
+    int rest, nact;
+    double* cp = c.take<double>(8 * CH_STRIDE);   // [W][16 * CH_STRIDE] from here: per wave 8 point rows, then 8 line rows
+    double* cl = c.take<double>(8 * CH_STRIDE);   // wave 0's line rows
+    double* more = c.take<double>(rest);          // the other waves' rows / the sort buffer's tail
+    double* buf = cp;                             // = cp: [NP2] MAD sort buffer
+    uint8_t* act = c.take<uint8_t>(nact);         // [mpt_cap + mls_cap, 16-B padded] active flags
+    uint8_t* pad = c.take<uint8_t>(16);
+    int bytes = c.off;
+    GFPL_HD PoseLds(unsigned char* smem, int W, int NP2, int mpt_cap, int mls_cap)
+        : c(smem), rest(region(W, NP2) - 16 * CH_STRIDE), nact((mpt_cap + mls_cap + 15) & ~15) {}
+};
+
+// ---- k_orb_cellfast: one cell per wave, byte cells
+struct OrbCellLds {
+    LdsCarver c;
+    int patch_cap, waves, wave;
+    uint8_t* below = c.take<uint8_t>(wave * 4 * patch_cap);   // the lower waves' cells
+    uint8_t* P = c.take<uint8_t>(patch_cap);                  // the cell's ROI
+    uint8_t* Sc = c.take<uint8_t>(patch_cap);                 // FAST scores
+    uint16_t* cand = c.take<uint16_t>(patch_cap);             // candidate list
+    uint8_t* above = c.take<uint8_t>((waves - 1 - wave) * 4 * patch_cap);
+    int bytes = c.off;
+    GFPL_HD OrbCellLds(unsigned char* smem, int patch_cap, int waves, int wave)
+        : c(smem), patch_cap(patch_cap), waves(waves), wave(wave) {}
+};
+
+// ---- k_lsd_grow_lds: one wave per image
+struct LsdGrowLds {
+    LdsCarver c;
+    int cid_cap;
+    uint32_t* ring = c.take<uint32_t>(LSD_RING);       // the region list's newest entries
+    uint32_t* used = c.take<uint32_t>(cid_cap / 32);   // compact used bitmap
+    int bytes = c.off;
+    GFPL_HD LsdGrowLds(unsigned char* smem, int cid_cap) : c(smem), cid_cap(cid_cap) {}
+};
+
+}  // namespace gfpl

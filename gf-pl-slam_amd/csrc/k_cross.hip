@@ -53,12 +53,7 @@ __global__ void __launch_bounds__(64) k_predict_pose(KParams p) {
     }
 }
 
-// dynamic LDS: prevT[16] Tinv[16] f64 | (XL) spxy[cap] f64x2 | cnt[ncell+2] start[ncell+2] i32 |
-//              sq[cap] i32 | spx[cap] spy[cap] f32 | lastT[cap] i32 | misc[64] i32
-// XL: the exact projections of the bucketed points in LDS too (bucket order, beside their float
-// copies), so a candidate that passes the float pre-filter reads them from LDS instead of an L2
-// round trip ahead of its descriptor load; for capacities whose LDS then leaves two workgroups
-// per CU (kp_cap <= 2048)
+// dynamic LDS: CrossPointsLds (gfpl_layout.hpp)
 #ifndef GFPL_CP_WAVES
 #define GFPL_CP_WAVES 8   // 2 workgroups / CU (84-B spill; 3.2 -> 2.6 ms measured)
 #endif
@@ -71,16 +66,11 @@ __global__ void __launch_bounds__(1024, GFPL_CP_WAVES) k_cross_points(KParams p,
     const int b = blockIdx.x;
     const int cap = p.kp_cap;
     const int NB = G.ncell + 1;   // buckets incl. wild
-    double* prevT = (double*)smem;
-    double* Tinv = prevT + 16;
-    double2* spxy = reinterpret_cast<double2*>(Tinv + 16);   // (XL)
-    int* cnt = (int*)(XL ? reinterpret_cast<double*>(spxy + cap) : Tinv + 16);
-    int* start = cnt + NB + 1;
-    int* sq = start + NB + 1;
-    float* spx = (float*)(sq + cap);
-    float* spy = spx + cap;
-    int* lastT = (int*)(spy + cap);
-    int* misc = lastT + cap;
+    const CrossPointsLds S(smem, cap, G.ncell, XL);
+    double *const prevT = S.prevT, *const Tinv = S.Tinv;
+    double2* const spxy = reinterpret_cast<double2*>(S.spxy);   // (XL)
+    int *const cnt = S.cnt, *const start = S.start, *const sq = S.sq, *const lastT = S.lastT, *const misc = S.misc;
+    float *const spx = S.spx, *const spy = S.spy;
     const int tid = threadIdx.x;
     const int Sp = p.prev.pt.n[b], Sc = p.curr.pt.n[b];
     if (tid < 16) {   // k_predict_pose wrote curr.Tfw and its inverse
@@ -230,8 +220,7 @@ __device__ __forceinline__ void knn2_lds(const uint32_t* q, const uint32_t* T, i
 }
 
 
-// dynamic LDS: knn LUT | tb[cap*8] u32 (train rows: curr, knn_stage_views) |
-//              i12 d0 d1 i21 [cap] | h12[260] h0[260] | misc[64]
+// dynamic LDS: CrossLinesLds (gfpl_layout.hpp)
 #ifndef GFPL_CL_WAVES
 #define GFPL_CL_WAVES 1
 #endif
@@ -240,10 +229,12 @@ __global__ void __launch_bounds__(BLOCK, GFPL_CL_WAVES) k_cross_lines(KParams p)
     extern __shared__ __align__(16) unsigned char smem[];
     const int b = blockIdx.x;
     const int cap = p.kl_cap;
-    // knn2_mfma<.., LUT0 = true> below REQUIRES the table at LDS address 0: first in the dynamic LDS, and
-    // no static __shared__ in this kernel (gfpl_knn.hpp)
+    // CrossLinesLds' fields by hand (as k_pose: built from the struct, the compiler schedules this
+    // kernel differently and the stage measured 1% slower); tests/test_layouts.py pins the struct, which
+    // the launcher sizes the launch from, to this walk.  knn2_mfma<.., LUT0 = true> below needs the table
+    // at LDS address 0: first in the dynamic LDS, and no static __shared__ in this kernel
     uint32_t* lut = (uint32_t*)smem;
-    uint32_t* tb = lut + knn_lut_dwords<1>();
+    uint32_t* tb = lut + knn_lut_dwords(1);
     int* i12 = (int*)(tb + cap * 8);
     int* d012 = i12 + cap;
     int* d112 = d012 + cap;
@@ -343,31 +334,33 @@ CrossGrid cross_grid(const KParams& p) {
     return G;
 }
 
-size_t cross_points_lds(const KParams& p, const CrossGrid& G, bool xl) {
-    return 32 * 8 + (size_t)(G.ncell + 2) * 8 + (size_t)p.kp_cap * (xl ? 32 : 16) + 64 * 4;
-}
-
 hipError_t launch_cross_points(const KParams& p, hipStream_t s) {
     const CrossGrid G = cross_grid(p);
     hipLaunchKernelGGL(k_predict_pose, dim3((p.B + 63) / 64), dim3(64), 0, s, p);
-    const size_t lxl = cross_points_lds(p, G, true);
+    const size_t lxl = CrossPointsLds(nullptr, p.kp_cap, G.ncell, true).bytes;
+    static std::atomic<unsigned long long> attr[2];   // (dynamic LDS above the 64 KB default)
     if (GFPL_CP_XL && p.kp_cap <= 2048 && lxl <= 80 * 1024) {
-        static std::atomic<unsigned long long> attr{0};
-        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_cross_points<true>), (int)lxl, &attr);
+        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_cross_points<true>), DYN_LDS_CEILING, &attr[1]);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_cross_points<true>, dim3(p.B), dim3(1024), lxl, s, p, G);
     } else {
-        hipLaunchKernelGGL(k_cross_points<false>, dim3(p.B), dim3(1024), cross_points_lds(p, G, false), s, p, G);
+        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_cross_points<false>), DYN_LDS_CEILING, &attr[0]);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_cross_points<false>, dim3(p.B), dim3(1024),
+                           CrossPointsLds(nullptr, p.kp_cap, G.ncell, false).bytes, s, p, G);
     }
     return hipGetLastError();
 }
 
 hipError_t launch_cross_lines(const KParams& p, hipStream_t s) {
-    const size_t lds = (size_t)p.kl_cap * 32 + (size_t)p.kl_cap * 16 + 520 * 4 + 64 * 4 + knn_lut_dwords<1>() * 4;
+    const size_t lds = CrossLinesLds(nullptr, p.kl_cap).bytes;
     // large-capacity LDS layout (one workgroup per CU) and small batches: 16 waves
-    if (p.kl_cap > 1024 || p.B <= sp_wide_max_b())
+    if (p.kl_cap > 1024 || p.B <= sp_wide_max_b()) {
+        static std::atomic<unsigned long long> attr{0};   // (dynamic LDS above the 64 KB default)
+        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_cross_lines<1024>), DYN_LDS_CEILING, &attr);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_cross_lines<1024>, dim3(p.B), dim3(1024), lds, s, p);
-    else
+    } else
         hipLaunchKernelGGL(k_cross_lines<512>, dim3(p.B), dim3(512), lds, s, p);
     return hipGetLastError();
 }

@@ -329,12 +329,15 @@ extern "C" int gfpl_lbd_create(gfpl_ctx* ctx, int width, int height, int max_ima
                 if (!(i <= 1 && j >= 7)) d.pairs[c++] = i | (j << 4);
     }
     const size_t npx = (size_t)width * height, M = (size_t)max_images;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t b_g = al(4 * M * npx);
-    if (hipMalloc(&o->base, b_g + 256) != hipSuccess) { delete o; return GFPL_E_HIP; }
-    char* p = (char*)o->base;
-    d.grad = (uint32_t*)p; p += b_g;
-    d.err = (int*)p;
+    auto layout = [&](Carver& c) {
+        d.grad = c.take<uint32_t>(M * npx);
+        d.err = c.take<int>(1);
+    };
+    Carver c;
+    layout(c);   // sizing pass (base == nullptr)
+    if (hipMalloc(&o->base, c.off) != hipSuccess) { delete o; return GFPL_E_HIP; }
+    c = Carver{0, (char*)o->base};
+    layout(c);
     if (o->st.init(d.err, o->stream) != hipSuccess) { o->st.destroy(); (void)hipFree(o->base); delete o; return GFPL_E_HIP; }
     o->ctx = ctx;
     gfpl_ctx_attach(ctx);

@@ -35,7 +35,6 @@ namespace gfpl {
 
 // ranges up to CAP elements are sorted in LDS: CAP 1024 (36.5 KB per two-wave workgroup, 4 images
 // per CU) for batches up to 4 images per CU, CAP 512 (24 KB, 6 per CU) above (k_lsd_sort<CAP>)
-#define LSD_RING 256               // region list entries mirrored in LDS
 #define LSD_SMALL 64               // ranges up to this size: one lane runs libstdc++'s serial loop
                                    // (32 / 48 / 64 / 96: 22.2k / 23.5k / 23.7k / 23.1k images/s)
 #ifndef GFPL_LSD_PRIO
@@ -1507,9 +1506,10 @@ __device__ void lsd_image(const LsdDev& o, int img, uint32_t* bits, uint32_t* ri
 // after the ring) for the images with at most cid_cap defined pixels, the HBM byte map for the
 // others (separate kernels: one holding both paths took 184 VGPRs and a private segment)
 __global__ void __launch_bounds__(64) k_lsd_grow_lds(LsdDev o) {
-    extern __shared__ uint32_t lds[];
+    extern __shared__ __align__(16) unsigned char lds[];
     if (o.ndef[blockIdx.x] > o.cid_cap) return;
-    lsd_image<true>(o, blockIdx.x, lds + LSD_RING, lds);
+    const LsdGrowLds S(lds, o.cid_cap);
+    lsd_image<true>(o, blockIdx.x, S.used, S.ring);
 }
 __global__ void __launch_bounds__(64) k_lsd_grow_glb(LsdDev o) {
     __shared__ uint32_t ring[LSD_RING];
@@ -1645,36 +1645,34 @@ extern "C" int gfpl_lsd_create(gfpl_ctx* ctx, const gfpl_lsd_params* prm, int wi
     // the compact used map covers a quarter of the pixels defined (VGA: 9.6 KB; the scenes
     // measured define 5-8%), so 15 images share a CU's LDS instead of 4 with a full-image bitmap
     d.cid_cap = (int)std::min<size_t>(((px + 3) / 4 + 31) & ~(size_t)31, LSD_CID_MAX);
-    o->lds_bytes = (size_t)d.cid_cap / 8 + 4 * LSD_RING;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t b_tab = al(16 * 1021 * 1021), b_px = al(16 * M * px), b_scs = al(8 * M * px), b_ang = al(4 * M * px), b_max = al(8 * M),
-                 b_keys = al(8 * M * NP), b_pos = al(4 * M * NP), b_reg = al(4 * M * px),
-                 b_used = al(M * px), b_segs = al(16 * M * SC), b_nseg = al(4 * M),
-                 b_klt = al(24 * M * SC), b_rk = al(8 * M * SC), b_rl = al(4 * M * SC);
-    const size_t total = b_tab + b_px + b_scs + b_ang + b_max + b_keys + 2 * b_pos + 3 * b_reg + b_used + b_segs + 2 * b_nseg +
-                         b_klt + b_rk + 2 * b_rl + 256;
-    if (hipMalloc(&o->base, total) != hipSuccess) { delete o; return GFPL_E_HIP; }
-    char* p = (char*)o->base;
-    d.cs_tab = (float4*)p; p += b_tab;
-    d.px = (float4*)p; p += b_px;
-    d.scs = (float2*)p; p += b_scs;
-    d.ang = (float*)p; p += b_ang;
-    d.maxg = (unsigned long long*)p; p += b_max;
-    d.keys = (uint64_t*)p; p += b_keys;
-    d.lpos = (int*)p; p += b_pos;
-    d.rpos = (int*)p; p += b_pos;
-    d.reg = (uint32_t*)p; p += b_reg;
-    d.tmp = (uint32_t*)p; p += b_reg;
-    d.cid = (uint32_t*)p; p += b_reg;
-    d.used_g = (uint8_t*)p; p += b_used;
-    d.segs = (float4*)p; p += b_segs;
-    d.nseg = (int*)p; p += b_nseg;
-    d.ndef = (int*)p; p += b_nseg;
-    d.kl_tmp = (float*)p; p += b_klt;
-    d.rkeys = (uint64_t*)p; p += b_rk;
-    d.rl = (int*)p; p += b_rl;
-    d.rr = (int*)p; p += b_rl;
-    d.err = (int*)p;
+    o->lds_bytes = LsdGrowLds(nullptr, d.cid_cap).bytes;
+    auto layout = [&](Carver& c) {
+        d.cs_tab = c.take<float4>(1021 * 1021);
+        d.px = c.take<float4>(M * px);
+        d.scs = c.take<float2>(M * px);
+        d.ang = c.take<float>(M * px);
+        d.maxg = c.take<unsigned long long>(M);
+        d.keys = c.take<uint64_t>(M * NP);
+        d.lpos = c.take<int>(M * NP);
+        d.rpos = c.take<int>(M * NP);
+        d.reg = c.take<uint32_t>(M * px);
+        d.tmp = c.take<uint32_t>(M * px);
+        d.cid = c.take<uint32_t>(M * px);
+        d.used_g = c.take<uint8_t>(M * px);
+        d.segs = c.take<float4>(M * SC);
+        d.nseg = c.take<int>(M);
+        d.ndef = c.take<int>(M);
+        d.kl_tmp = c.take<float>(6 * M * SC);
+        d.rkeys = c.take<uint64_t>(M * SC);
+        d.rl = c.take<int>(M * SC);
+        d.rr = c.take<int>(M * SC);
+        d.err = c.take<int>(1);
+    };
+    Carver c;
+    layout(c);   // sizing pass (base == nullptr)
+    if (hipMalloc(&o->base, c.off) != hipSuccess) { delete o; return GFPL_E_HIP; }
+    c = Carver{0, (char*)o->base};
+    layout(c);
     if (hipFuncSetAttribute((const void*)k_lsd_grow_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)o->lds_bytes) != hipSuccess) {
         (void)hipFree(o->base);

@@ -464,9 +464,9 @@ __global__ void __launch_bounds__(256) k_orb_cellfast(OrbDev o) {
     const int c = blockIdx.x * (blockDim.x >> 6) + wave, img = blockIdx.y;
     if (c >= o.ncell) return;
     // byte cells (dword cells triple the LDS and halve the occupancy: measured 1.9x slower)
-    uint8_t* P = csm + wave * 4 * o.patch_cap;
-    uint8_t* Sc = P + o.patch_cap;
-    uint16_t* cand = reinterpret_cast<uint16_t*>(Sc + o.patch_cap);
+    const OrbCellLds Y(csm, o.patch_cap, blockDim.x >> 6, wave);
+    uint8_t *const P = Y.P, *const Sc = Y.Sc;
+    uint16_t* const cand = Y.cand;
     int l = 0;
     while (c >= o.cbase[l + 1]) ++l;
     const OrbLevel& L = o.lv[l];
@@ -1081,6 +1081,38 @@ void resize_tables(OrbDev& d, std::vector<int>& xofs_h, std::vector<int16_t>& al
     }
 }
 
+// the four tables on the device (each with 4 B of slack past its last entry)
+struct ResizeTabs {
+    int* xofs;
+    int16_t* alpha;
+    int* yofs;
+    int16_t* beta;
+};
+ResizeTabs resize_tabs_layout(Carver& c, size_t nx, size_t na, size_t ny, size_t nb) {
+    ResizeTabs T;
+    T.xofs = c.take<int>(nx + 1);
+    T.alpha = c.take<int16_t>(na + 2);
+    T.yofs = c.take<int>(ny + 1);
+    T.beta = c.take<int16_t>(nb + 2);
+    return T;
+}
+// copies the tables and points d's levels 1.. at them
+bool resize_tabs_upload(OrbDev& d, const ResizeTabs& T, const std::vector<int>& xofs_h, const std::vector<int16_t>& alpha_h,
+                        const std::vector<int>& yofs_h, const std::vector<int16_t>& beta_h, const long long* xoff,
+                        const long long* yoff) {
+    for (int l = 1; l < d.nlevels; ++l) {
+        d.xofs[l] = T.xofs + xoff[l];
+        d.alpha[l] = T.alpha + 2 * xoff[l];
+        d.yofs[l] = T.yofs + yoff[l];
+        d.beta[l] = T.beta + 2 * yoff[l];
+    }
+    if (xofs_h.empty()) return true;
+    return hipMemcpy(T.xofs, xofs_h.data(), 4 * xofs_h.size(), hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemcpy(T.alpha, alpha_h.data(), 2 * alpha_h.size(), hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemcpy(T.yofs, yofs_h.data(), 4 * yofs_h.size(), hipMemcpyHostToDevice) == hipSuccess &&
+           hipMemcpy(T.beta, beta_h.data(), 2 * beta_h.size(), hipMemcpyHostToDevice) == hipSuccess;
+}
+
 }  // namespace
 
 extern "C" int gfpl_orb_create(gfpl_ctx* ctx, int width, int height, const gfpl_orb_params* prm, int max_images,
@@ -1191,7 +1223,7 @@ extern "C" int gfpl_orb_create(gfpl_ctx* ctx, int width, int height, const gfpl_
     d.key_lds = std::max(0, (int)((40 * 1024 - (long long)orb_octree_lds(d.node_cap, 0)) / 4) & ~63);
     if (orb_octree_lds(d.node_cap, d.key_lds) > 160 * 1024 - 64) { delete o; return GFPL_E_UNSUPPORTED; }
     if (hipFuncSetAttribute((const void*)k_orb_cellfast, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            4 * d.patch_cap * d.cell_waves) !=
+                            (int)OrbCellLds(nullptr, d.patch_cap, d.cell_waves, 0).bytes) !=
         hipSuccess) { delete o; return GFPL_E_HIP; }
     if (hipFuncSetAttribute((const void*)k_orb_octree, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)orb_octree_lds(d.node_cap, d.key_lds)) != hipSuccess) { delete o; return GFPL_E_HIP; }
@@ -1212,46 +1244,28 @@ extern "C" int gfpl_orb_create(gfpl_ctx* ctx, int width, int height, const gfpl_
     if (rz_max > 160 * 1024 - 64) { delete o; return GFPL_E_UNSUPPORTED; }
     if (rz_max > 0 && hipFuncSetAttribute((const void*)k_orb_resize, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           rz_max) != hipSuccess) { delete o; return GFPL_E_HIP; }
-    // one allocation: tables | pyr | blur | ckeys | ccnt | keys | tmp | nkeys | nsel | sel | err
-    const long long M = max_images;
-    auto al = [](long long v) { return (v + 255) & ~255LL; };
-    const long long b_x = al(4 * (long long)xofs_h.size() + 4), b_a = al(2 * (long long)alpha_h.size() + 4);
-    const long long b_y = al(4 * (long long)yofs_h.size() + 4), b_b = al(2 * (long long)beta_h.size() + 4);
-    const long long b_img = al(M * d.pyr_stride);
-    const long long b_keys = al(4 * M * d.nlevels * (long long)d.key_cap);
-    const long long b_n = al(4 * M * d.nlevels);
-    const long long b_sel = al(4 * M * d.nlevels * (long long)d.sel_cap);
-    const long long b_ck = al(4 * M * d.ncell * (long long)d.ccap), b_cc = al(4 * M * d.ncell);
-    const long long total = b_x + b_a + b_y + b_b + 2 * b_img + 2 * b_keys + 2 * b_n + b_sel + b_ck + b_cc + 256;
-    if (hipMalloc(&o->base, (size_t)total) != hipSuccess) { delete o; return GFPL_E_HIP; }
-    char* p = (char*)o->base;
-    int* xo = (int*)p; p += b_x;
-    int16_t* ap = (int16_t*)p; p += b_a;
-    int* yo = (int*)p; p += b_y;
-    int16_t* bp = (int16_t*)p; p += b_b;
-    d.pyr = (uint8_t*)p; p += b_img;
-    d.blur = (uint8_t*)p; p += b_img;
-    d.ckeys = (uint32_t*)p; p += b_ck;
-    d.ccnt = (int*)p; p += b_cc;
-    d.keys = (uint32_t*)p; p += b_keys;
-    d.tmp = (uint32_t*)p; p += b_keys;
-    d.nkeys = (int*)p; p += b_n;
-    d.nsel = (int*)p; p += b_n;
-    d.sel = (uint32_t*)p; p += b_sel;
-    d.err = (int*)p;
-    for (int l = 1; l < d.nlevels; ++l) {
-        d.xofs[l] = xo + xoff[l];
-        d.alpha[l] = ap + 2 * xoff[l];
-        d.yofs[l] = yo + yoff[l];
-        d.beta[l] = bp + 2 * yoff[l];
-    }
-    bool ok = true;
-    if (!xofs_h.empty()) {
-        ok = ok && hipMemcpy(xo, xofs_h.data(), 4 * xofs_h.size(), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipMemcpy(ap, alpha_h.data(), 2 * alpha_h.size(), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipMemcpy(yo, yofs_h.data(), 4 * yofs_h.size(), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipMemcpy(bp, beta_h.data(), 2 * beta_h.size(), hipMemcpyHostToDevice) == hipSuccess;
-    }
+    // one allocation: the resize tables, then the extractor's buffers
+    ResizeTabs T;
+    auto layout = [&](Carver& c) {
+        const size_t M = max_images, ML = M * d.nlevels, MC = M * d.ncell;
+        T = resize_tabs_layout(c, xofs_h.size(), alpha_h.size(), yofs_h.size(), beta_h.size());
+        d.pyr = c.take<uint8_t>(M * d.pyr_stride);
+        d.blur = c.take<uint8_t>(M * d.pyr_stride);
+        d.ckeys = c.take<uint32_t>(MC * d.ccap);
+        d.ccnt = c.take<int>(MC);
+        d.keys = c.take<uint32_t>(ML * d.key_cap);
+        d.tmp = c.take<uint32_t>(ML * d.key_cap);
+        d.nkeys = c.take<int>(ML);
+        d.nsel = c.take<int>(ML);
+        d.sel = c.take<uint32_t>(ML * d.sel_cap);
+        d.err = c.take<int>(1);
+    };
+    Carver c;
+    layout(c);   // sizing pass (base == nullptr)
+    if (hipMalloc(&o->base, c.off) != hipSuccess) { delete o; return GFPL_E_HIP; }
+    c = Carver{0, (char*)o->base};
+    layout(c);
+    bool ok = resize_tabs_upload(d, T, xofs_h, alpha_h, yofs_h, beta_h, xoff, yoff);
     ok = ok && hipMemcpyToSymbol(HIP_SYMBOL(c_orb_pattern), kOrbPattern, sizeof(kOrbPattern)) == hipSuccess;
     if (!ok || o->st.init(d.err, o->stream) != hipSuccess) { o->st.destroy(); (void)hipFree(o->base); delete o; return GFPL_E_HIP; }
     gfpl_ctx_attach(ctx);
@@ -1298,28 +1312,13 @@ int pyrbuild_create(const gfpl_camera* cam, PyrBuild** out) {
     if (rz_max > 160 * 1024 - 64) { delete pb; return GFPL_E_UNSUPPORTED; }
     if (rz_max > 0 && hipFuncSetAttribute((const void*)k_orb_resize, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           rz_max) != hipSuccess) { delete pb; return GFPL_E_HIP; }
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t bx = al(4 * xofs_h.size() + 4), ba = al(2 * alpha_h.size() + 4), by = al(4 * yofs_h.size() + 4),
-                 bb = al(2 * beta_h.size() + 4);
-    if (hipMalloc(&pb->tables, bx + ba + by + bb) != hipSuccess) { delete pb; return GFPL_E_HIP; }
-    char* q = (char*)pb->tables;
-    int* xo = (int*)q;
-    int16_t* ap = (int16_t*)(q + bx);
-    int* yo = (int*)(q + bx + ba);
-    int16_t* bp = (int16_t*)(q + bx + ba + by);
-    bool ok = true;
-    if (!xofs_h.empty()) {
-        ok = ok && hipMemcpy(xo, xofs_h.data(), 4 * xofs_h.size(), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipMemcpy(ap, alpha_h.data(), 2 * alpha_h.size(), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipMemcpy(yo, yofs_h.data(), 4 * yofs_h.size(), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipMemcpy(bp, beta_h.data(), 2 * beta_h.size(), hipMemcpyHostToDevice) == hipSuccess;
-    }
-    if (!ok) { (void)hipFree(pb->tables); delete pb; return GFPL_E_HIP; }
-    for (int l = 1; l < d.nlevels; ++l) {
-        d.xofs[l] = xo + xoff[l];
-        d.alpha[l] = ap + 2 * xoff[l];
-        d.yofs[l] = yo + yoff[l];
-        d.beta[l] = bp + 2 * yoff[l];
+    Carver c;
+    resize_tabs_layout(c, xofs_h.size(), alpha_h.size(), yofs_h.size(), beta_h.size());   // sizing pass
+    if (hipMalloc(&pb->tables, c.off) != hipSuccess) { delete pb; return GFPL_E_HIP; }
+    c = Carver{0, (char*)pb->tables};
+    const ResizeTabs T = resize_tabs_layout(c, xofs_h.size(), alpha_h.size(), yofs_h.size(), beta_h.size());
+    if (!resize_tabs_upload(d, T, xofs_h, alpha_h, yofs_h, beta_h, xoff, yoff)) {
+        (void)hipFree(pb->tables); delete pb; return GFPL_E_HIP;
     }
     *out = pb;
     return GFPL_OK;
@@ -1378,7 +1377,7 @@ extern "C" int gfpl_orb_extract_async(gfpl_orb* o, const uint8_t* images, int n,
     hipLaunchKernelGGL(k_orb_blur, dim3((L0.w + BLUR_TW - 1) / BLUR_TW, (L0.h + BLUR_TH - 1) / BLUR_TH, n * d.nlevels),
                        dim3(256), 0, s, d);
     hipLaunchKernelGGL(k_orb_cellfast, dim3((d.ncell + d.cell_waves - 1) / d.cell_waves, n), dim3(64 * d.cell_waves),
-                       4 * d.patch_cap * d.cell_waves, s, d);
+                       OrbCellLds(nullptr, d.patch_cap, d.cell_waves, 0).bytes, s, d);
     hipLaunchKernelGGL(k_orb_gather, dim3(n * d.nlevels), dim3(GATHER_T), 0, s, d);
     const size_t lds = orb_octree_lds(d.node_cap, d.key_lds);
     hipLaunchKernelGGL(k_orb_octree, dim3(n * d.nlevels), dim3(64), lds, s, d);

@@ -127,10 +127,9 @@ __device__ __attribute__((noinline)) void se3_update_wave(const double* inc, dou
 }
 
 #define PT_K 6    // X Y Z ox oy sigma2
-// chunk rows are 66 doubles (528 B) apart: the reduction lanes read rows ia, ib
+// chunk rows are CH_STRIDE = 66 doubles (528 B) apart: the reduction lanes read rows ia, ib
 // of the same columns k, k + 1 as 16-B pairs, and a 64-double stride would put
 // every row in the same LDS bank
-#define CH_STRIDE 66
 // register budget of the GN loop (DESIGN.md §4 k_pose): DT read from LDS, the next chunk's
 // inputs prefetched into registers and a 4-deep reduction unroll: 149 VGPRs (3 waves /
 // SIMD, which the ~10 KB LDS workgroup allows), 7.3 -> 6.9 ms measured; without the
@@ -675,7 +674,7 @@ __device__ __forceinline__ int line_outliers_regs(const KParams& p, const double
     return wave_sum(ol);
 }
 
-// dynamic LDS: {cp[8*CH_STRIDE] cl[8*CH_STRIDE] | buf[NP2]} f64 | act[mpt+mls] u8 (16-B padded):
+// dynamic LDS: PoseLds (gfpl_layout.hpp):
 // 9.3 KB + 576 B static at the default caps (500 / 300), so 16 waves fit a CU's 160 KB (4 per
 // SIMD, as the 122 VGPRs allow); the compacted positions gauss_newton walks live in HBM
 #ifndef GFPL_POSE_WAVES
@@ -688,8 +687,10 @@ __global__ void __launch_bounds__(64 * W, W == 1 ? GFPL_POSE_WAVES : 1) k_pose(K
     const int b = blockIdx.x;
     const int lane = threadIdx.x;   // (W > 1: wave 0's lanes; the helpers branch off below)
     const int npt = p.tr.n_matched_pt[b], nls = p.tr.n_matched_ls[b];
-    // the GN chunk rows and the outlier residuals are never live together
-    const int region = max(W * 16 * CH_STRIDE, NP2);
+    // PoseLds' fields by hand, sharing its region(): built from the struct, the kernel's LDS
+    // addresses stop being compile-time constants where the compiler specialises the GN helpers
+    // (18 more ds_* instructions and other registers); tests/test_layouts.py pins these offsets
+    const int region = PoseLds::region(W, NP2);
     double* cp = (double*)smem;
     double* cl = cp + 8 * CH_STRIDE;
     double* buf = cp;   // MAD sort buffer: never live together with the GN chunk rows
@@ -1026,11 +1027,10 @@ hipError_t launch_pose(const KParams& p, hipStream_t s, hipEvent_t mark) {
     const bool w8 = p.B <= pose_w8_max_b();
     const bool multi = p.B <= pose_multi_max_b();   // small batches: POSE_W waves per sequence
     const int Wl = w8 ? 8 : (multi ? POSE_W : 1);
-    const size_t region = (size_t)std::max(Wl * 16 * CH_STRIDE, NP2);
-    const size_t lds = region * 8 + ((p.mpt_cap + p.mls_cap + 15) & ~15) + 16;
+    const size_t lds = PoseLds(nullptr, Wl, NP2, p.mpt_cap, p.mls_cap).bytes;
     if (w8) {
         static std::atomic<unsigned long long> attr{0};   // (dynamic LDS above the 64 KB default)
-        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_pose<8>), 160 * 1024 - 1024, &attr);
+        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_pose<8>), DYN_LDS_CEILING, &attr);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_pose<8>, dim3(p.B), dim3(64 * 8), lds, s, p, NP2);
     } else if (multi)

@@ -211,20 +211,17 @@ __device__ __forceinline__ void sad_finish(const KParams& p, const SadJob& J, fl
 #ifndef GFPL_SP_WAVES
 #define GFPL_SP_WAVES 6   // waves per SIMD: <= 84 VGPRs; LDS holds three 512-thread workgroups per CU (6 waves per SIMD)
 #endif
-#define SP_CHUNK 32       // sorted right-keypoint entries per staged descriptor chunk (k_stereo_points, SEG)
 #ifndef GFPL_SP_TY
 #define GFPL_SP_TY 3      // SAD job tiles (SEG): 2^TY rows x 2^TX columns, coarser when the bins exceed 4094
 #endif
 #ifndef GFPL_SP_TX
 #define GFPL_SP_TX 6
 #endif
-#define SP_MINR_PAD 32    // minr bins span [-PAD, H + PAD) (k_stereo_points, SEG): every band is shorter
 
 // LDS-only wave sync: the wave's earlier LDS writes / reads have completed (LDS executes a
 // wave's accesses in order; the clobber keeps the compiler from moving accesses across it)
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-// dynamic LDS: rkey[KP2] u32 | order[KP2] u32 | pairs[KP2] u32 | recx[KP2] f32 |
-//              recm[KP2] u16 | rowlo[nRows] u16 | misc[64] i32 | (SEG) stage[waves][SP_CHUNK][32 B]
+// dynamic LDS: StereoPointsLds (gfpl_layout.hpp)
 // Right keypoints are sorted by their row band start (the reference's
 // vRowIndices buckets, src/stereoFrame.cpp:459-485) and their x, octave and band
 // height are copied next to the sorted keys, so the band scan of a left keypoint
@@ -261,22 +258,13 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SP_WAVES) k_stereo_points(KParams 
     const int b = blockIdx.x;
     const int cap = p.kp_cap;
     const int nRows = p.cam.height;
-    uint32_t* rkey = (uint32_t*)smem;
-    uint32_t* order = rkey + KP2;
-    uint32_t* pairs = order + KP2;
-    float* recx = (float*)(pairs + KP2);
-    uint16_t* recm = (uint16_t*)(recx + KP2);
-    uint16_t* rowlo = recm + KP2;   // SEG: offr, the bin offsets of the counting sort
     const int nlev = p.cam.n_levels;
-    const int NBIN = nRows + 2 * SP_MINR_PAD;   // SEG: minr bins per octave segment
-    const int nrl = SEG ? (nlev + 1) * NBIN + 1 : nRows;
-    int* misc = (int*)(rowlo + ((nrl + 1) & ~1));   // SEG: [22 + seg] band heights
-    // SEG: per-wave staging of right descriptors, SP_CHUNK x 32 B per wave (16-B aligned); an
-    // integer offset from smem keeps the pointer in the LDS address space
-    uint32_t* stg = (uint32_t*)(smem + ((KP2 * 18 + ((nrl + 1) & ~1) * 2 + 32 * 4 + 15) & ~15));
-    // mvDepth of the sub-pixel pass lives in recx: the right keypoints' x are dead once the
-    // band scan is over (LDS, no scattered 4-B global stores)
-    float* depth = recx;
+    const StereoPointsLds S(smem, KP2, nRows, nlev, SEG, BLOCK / 64);
+    uint32_t *const rkey = S.rkey, *const order = S.order, *const pairs = S.pairs, *const stg = S.stg;
+    float *const recx = S.recx, *const depth = S.depth;   // (depth in LDS: no scattered 4-B global stores)
+    uint16_t *const recm = S.recm, *const rowlo = S.rowlo;
+    int* const misc = S.misc;
+    const int NBIN = S.nbin, nrl = S.nrl;
     const int tid = threadIdx.x;
     SP_CLK(0);
     SP_PRIO(3);
@@ -295,8 +283,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SP_WAVES) k_stereo_points(KParams 
         // in [0, H) and bands are shorter than PAD, so clamping never reorders a candidate
         // across a row's start or stop.  Left keypoints go in row order (the processing
         // order, which has no effect on the output).
-        uint32_t* hr = reinterpret_cast<uint32_t*>(rowlo);   // u16 counts, two per word
-        uint32_t* hl = stg;                                  // left row counts (u16), in the stage buffer
+        uint32_t *const hr = S.hr, *const hl = S.hl;   // u16 counts, two per word (hl in the stage buffer)
         const int nbr = (nlev + 1) * NBIN, nbl = nRows + 1;
         for (int w = tid; w < (nbr + 2) / 2; w += BLOCK) hr[w] = 0u;
         for (int w = tid; w < (nbl + 1) / 2; w += BLOCK) hl[w] = 0u;
@@ -343,8 +330,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SP_WAVES) k_stereo_points(KParams 
         }
         __syncthreads();
         // exclusive scans of both histograms in place (u16 offsets), block-wide
-        uint16_t* offr = rowlo;
-        uint16_t* offl = reinterpret_cast<uint16_t*>(hl);
+        uint16_t *const offr = S.offr, *const offl = S.offl;
         {   // one block scan for both: the right sums in the low, the left in the high 16 bits
             // (each total is at most kp_cap <= 2048, so the halves never carry into each other)
             const int pr = (nbr + BLOCK - 1) / BLOCK, r0 = min(tid * pr, nbr), r1 = min(r0 + pr, nbr);
@@ -963,9 +949,7 @@ __device__ __forceinline__ void knn2_row(const uint32_t* q, const uint32_t* T, i
     i0 = idx0; d0 = dist0; d1 = dist1;
 }
 
-// dynamic LDS: knn LUT | tb[cap*8] u32 (train rows R, knn_stage_views) |
-//              lr_i[cap] lr_d0 lr_d1 rl_i | hist[260] | misc[64]
-// Query rows stream from HBM into registers; only the train set sits in LDS, so
+// dynamic LDS: StereoLinesLds (gfpl_layout.hpp); only the train set sits in LDS, so
 // 2000 lines per side (config 5) fit.
 // diagnostic build (-DGFPL_SL_CLOCK): the phase boundaries' wall clock per sequence (scr.dbg): start,
 // train rows staged, knn pass, medians, end (tools/sp_phases.py --lines)
@@ -979,10 +963,12 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SL_WAVES) k_stereo_lines(KParams p
     extern __shared__ __align__(16) unsigned char smem[];
     const int b = blockIdx.x;
     const int cap = p.kl_cap;
-    // knn2_mfma<.., LUT0 = true> below REQUIRES the table at LDS address 0: first in the dynamic LDS, and
-    // no static __shared__ in this kernel (gfpl_knn.hpp)
+    // StereoLinesLds' fields by hand (as k_pose: built from the struct, the compiler schedules this
+    // kernel differently and the stage measured 1% slower); tests/test_layouts.py pins the struct, which
+    // the launcher sizes the launch from, to this walk.  knn2_mfma<.., LUT0 = true> below needs the table
+    // at LDS address 0: first in the dynamic LDS, and no static __shared__ in this kernel
     uint32_t* lut = (uint32_t*)smem;
-    uint32_t* tb = lut + knn_lut_dwords<CELL>();
+    uint32_t* tb = lut + knn_lut_dwords(CELL);
     int* lr_i = (int*)(tb + cap * 8);
     int* lr_d0 = lr_i + cap;
     int* lr_d1 = lr_d0 + cap;
@@ -1263,35 +1249,46 @@ int sp_wide_max_b() {
 
 hipError_t launch_stereo_points(const KParams& p, hipStream_t s) {
     const int KP2 = next_pow2(p.kp_cap);
-    const size_t lds = (size_t)KP2 * 18 + (size_t)((p.cam.height + 1) & ~1) * 2 + 64 * 4;
-    const int nrl_seg = (p.cam.n_levels + 1) * (p.cam.height + 2 * SP_MINR_PAD) + 1;
-    const size_t lds_seg = (size_t)KP2 * 18 + (size_t)((nrl_seg + 1) & ~1) * 2 + 32 * 4 + 16 +
-                           (size_t)(512 / 64) * SP_CHUNK * 32;
-    const size_t lds_seg_w = lds_seg + (size_t)(512 / 64) * SP_CHUNK * 32;   // (16 waves' staging)
+    auto lds_of = [&](bool seg, int waves) {
+        return (size_t)StereoPointsLds(nullptr, KP2, p.cam.height, p.cam.n_levels, seg, waves).bytes;
+    };
+    const size_t lds_seg = lds_of(true, 8), lds_seg_w = lds_of(true, 16);
     if (p.B <= sp_wide_max_b() && p.kp_cap <= 2048 && lds_seg_w <= 64 * 1024) {
         hipLaunchKernelGGL((k_stereo_points<1024, true>), dim3(p.B), dim3(1024), lds_seg_w, s, p, KP2);
         return hipGetLastError();
     }
     // the large-capacity layout leaves LDS for one workgroup per CU: give it 16 waves
-    if (p.kp_cap > 2048)
-        hipLaunchKernelGGL((k_stereo_points<1024, false>), dim3(p.B), dim3(1024), lds, s, p, KP2);
+    if (p.kp_cap > 2048) {
+        static std::atomic<unsigned long long> attr{0};   // (dynamic LDS above the 64 KB default)
+        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_stereo_points<1024, false>), DYN_LDS_CEILING, &attr);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_stereo_points<1024, false>), dim3(p.B), dim3(1024), lds_of(false, 16), s, p, KP2);
+    }
     else if (lds_seg <= 54 * 1024 && p.kp_cap <= 2048)   // three workgroups per CU
         hipLaunchKernelGGL((k_stereo_points<512, true>), dim3(p.B), dim3(512), lds_seg, s, p, KP2);
     else
-        hipLaunchKernelGGL((k_stereo_points<512, false>), dim3(p.B), dim3(512), lds, s, p, KP2);
+        hipLaunchKernelGGL((k_stereo_points<512, false>), dim3(p.B), dim3(512), lds_of(false, 8), s, p, KP2);
     return hipGetLastError();
 }
 
-// (the table of CELL 2, the larger one, for both instantiations)
-size_t stereo_lines_lds(int cap) { return (size_t)cap * 32 + (size_t)cap * 16 + 260 * 4 + 64 * 4 + knn_lut_dwords<2>() * 4; }
+// one k_stereo_lines instantiation; the 1024-thread forms alone run capacities whose layout exceeds 64 KB
+template <int CELL, bool INITIAL, int BLOCK>
+static hipError_t launch_stereo_lines_as(const KParams& p, hipStream_t s) {
+    if (BLOCK == 1024) {
+        static std::atomic<unsigned long long> attr{0};   // (dynamic LDS above the 64 KB default)
+        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(k_stereo_lines<CELL, INITIAL, BLOCK>),
+                                            DYN_LDS_CEILING, &attr);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((k_stereo_lines<CELL, INITIAL, BLOCK>), dim3(p.B), dim3(BLOCK),
+                       StereoLinesLds(nullptr, p.kl_cap, CELL).bytes, s, p);
+    return hipGetLastError();
+}
 
 hipError_t launch_stereo_lines(const KParams& p, hipStream_t s) {
     // large-capacity LDS layout (one workgroup per CU) and small batches: 16 waves
-    if (p.kl_cap > 1024 || p.B <= sp_wide_max_b())
-        hipLaunchKernelGGL((k_stereo_lines<2, false, 1024>), dim3(p.B), dim3(1024), stereo_lines_lds(p.kl_cap), s, p);
-    else
-        hipLaunchKernelGGL((k_stereo_lines<2, false, 512>), dim3(p.B), dim3(512), stereo_lines_lds(p.kl_cap), s, p);
-    return hipGetLastError();
+    if (p.kl_cap > 1024 || p.B <= sp_wide_max_b()) return launch_stereo_lines_as<2, false, 1024>(p, s);
+    return launch_stereo_lines_as<2, false, 512>(p, s);
 }
 
 hipError_t launch_line_uncertainty(const KParams& p, hipStream_t s) {
@@ -1312,10 +1309,9 @@ hipError_t launch_init(const KParams& p, hipStream_t s) {
                        p.in.pdesc_l, p.in.n_kp_l, 0, (size_t)cap, cap, (int32_t*)nullptr, (float*)nullptr,
                        lr + (size_t)cap * 3, (size_t)cap * 2);
     hipLaunchKernelGGL(k_init_points, dim3(p.B), dim3(512), 0, s, p);
-    if (p.kl_cap > 1024)
-        hipLaunchKernelGGL((k_stereo_lines<1, true, 1024>), dim3(p.B), dim3(1024), stereo_lines_lds(p.kl_cap), s, p);
-    else
-        hipLaunchKernelGGL((k_stereo_lines<1, true, 512>), dim3(p.B), dim3(512), stereo_lines_lds(p.kl_cap), s, p);
+    const hipError_t e = p.kl_cap > 1024 ? launch_stereo_lines_as<1, true, 1024>(p, s)
+                                         : launch_stereo_lines_as<1, true, 512>(p, s);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_init_pose, dim3((p.B + 63) / 64), dim3(64), 0, s, p);
     return hipGetLastError();
 }

@@ -183,6 +183,23 @@ def test_small_counts_parity():
     _check(rep)
 
 
+@pytest.mark.parametrize("sp_wide", ["0", None])
+@pytest.mark.parametrize("kp_cap,kl_cap", [(66, 34), (2048, 1024), (2050, 1026)])
+def test_layout_corner_capacities_parity(monkeypatch, kp_cap, kl_cap, sp_wide):
+    """Capacity, not count, drives the dynamic-LDS layouts (gfpl_layout.hpp): a few tens of features in
+    seqbatches whose capacities are not powers of two (KP2 rounds 66 -> 128, 2050 -> 4096) and sit on both
+    sides of the kernel switches (kp_cap 2048 | 2050: the SEG and XL forms | the large-capacity forms;
+    kl_cap 1024 | 1026: 8 | 16 waves), with the 8-wave stereo kernels (GFPL_SP_WIDE_MAX_B = 0) and the
+    default 16-wave ones."""
+    if sp_wide is None:
+        monkeypatch.delenv("GFPL_SP_WIDE_MAX_B", raising=False)
+    else:
+        monkeypatch.setenv("GFPL_SP_WIDE_MAX_B", sp_wide)
+    rep = _run_sequence("vga", {}, n_seq=2, n_frames=2, kp_cap=kp_cap, kl_cap=kl_cap,
+                        synth_over=dict(n_kp=48, n_kl=24, n_world_pts=64, n_world_lines=36), seed=23)
+    _check(rep)
+
+
 @pytest.mark.parametrize("nq,nt", [(33, 2), (5, 2049), (1000, 3000), (64, 31)])
 def test_knn2_hamming_shapes(nq, nt):
     """gfpl_knn2_hamming (MFMA path) on ragged tile shapes and a train set that spans
