@@ -30,9 +30,14 @@ hipError_t launch_stereo_points(const KParams& p, hipStream_t s);
 hipError_t launch_stereo_lines(const KParams& p, hipStream_t s);
 hipError_t launch_line_uncertainty(const KParams& p, hipStream_t s);
 hipError_t launch_init(const KParams& p, hipStream_t s);
+// k_match.hip: knn-2 of one descriptor set against another (idx / dist [nq][2]), and of B sequences'
+// sets at q / t + b * cap * 32 with counts min(nq[b], cap) / min(nt[b], cap) (device), packed
+// (idx0, d0, d1) at packed + b * cap * 6 (a frame's two directions share the sequence's block)
 hipError_t launch_knn2(const uint8_t* q, int nq, const uint8_t* t, int nt, int cell, int32_t* idx, float* dist,
                        hipStream_t s);
-// k_match.hip: radiusMatch rows (count pass, then the rows at row_off) and knn-2 list statistics
+hipError_t launch_knn2_batched(const uint8_t* q, const int* nq, const uint8_t* t, const int* nt, int cap, int B,
+                               int cell, int32_t* packed, hipStream_t s);
+// radiusMatch rows (count pass, then the rows at row_off) and knn-2 list statistics
 hipError_t launch_radius_count(const uint8_t* q, int nq, const uint8_t* t, int nt, int cell, float radius,
                                int32_t* cnt, hipStream_t s);
 hipError_t launch_radius_rows(const uint8_t* q, int nq, const uint8_t* t, int nt, int cell, float radius,

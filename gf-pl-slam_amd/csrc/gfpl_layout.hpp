@@ -17,11 +17,6 @@
 #define GFPL_HD
 #endif
 
-// GFPL_KNN_FP4 (gfpl_knn.hpp): the knn operands' number format sizes the expansion table
-#ifndef GFPL_KNN_FP4
-#define GFPL_KNN_FP4 1
-#endif
-
 namespace gfpl {
 
 // bump allocator over one device allocation (256-B aligned fields); base == nullptr: sizing pass
@@ -63,11 +58,10 @@ constexpr int SP_CHUNK = 32;      // sorted right-keypoint entries per staged de
 constexpr int SP_MINR_PAD = 32;   // minr bins span [-PAD, H + PAD) (k_stereo_points, SEG): every band is shorter
 constexpr int CH_STRIDE = 66;     // doubles per GN chunk row (k_pose)
 constexpr int LSD_RING = 256;     // region list entries mirrored in LDS (k_lsd_grow_*)
-constexpr bool KNN_FP4 = GFPL_KNN_FP4 != 0;
-// Expansion table for the train (A) side of the knn MFMA, one entry per byte value:
-// i8 : CELL 2: 4 dwords of one-hot cells (16 i8); CELL 1: 2 dwords of bits (8 i8)
-// FP4: CELL 2: 2 dwords (16 nibbles);             CELL 1: 1 dword (8 nibbles)
-GFPL_HD constexpr int knn_lut_entry_dwords(int cell) { return (cell == 2 ? 4 : 2) / (KNN_FP4 ? 2 : 1); }
+constexpr int KNN_CHUNK = 1024;   // train rows per staged chunk (k_knn2m)
+// Expansion table for the train (A) side of the knn MFMA (gfpl_knn.hpp), one entry of FP4 nibbles
+// per byte value: CELL 2: 2 dwords (4 one-hot cells, 16 nibbles); CELL 1: 1 dword (8 bits, 8 nibbles)
+GFPL_HD constexpr int knn_lut_entry_dwords(int cell) { return cell == 2 ? 2 : 1; }
 GFPL_HD constexpr int knn_lut_dwords(int cell) { return 256 * knn_lut_entry_dwords(cell); }
 
 // Every layout below is a struct whose members are the takes, in order (members initialise in
@@ -102,8 +96,8 @@ struct StereoPointsLds {
 };
 
 // ---- k_stereo_lines<CELL, INITIAL, BLOCK>, one layout for both cells.
-// THE KNN TABLE COMES FIRST: knn2_mfma<.., LUT0 = true> reads it at LDS address 0, so `lut` is the
-// first take and a kernel using this layout (or CrossLinesLds) declares no static __shared__.
+// THE KNN TABLE COMES FIRST: knn_tile (gfpl_knn.hpp) reads it at LDS address 0, so `lut` is the first
+// take and a kernel using this layout (or CrossLinesLds, Knn2Lds) declares no static __shared__.
 // Only the train rows sit in LDS (the query rows stream from HBM into registers).
 // (k_stereo_lines, k_cross_lines and k_pose still walk their pointers by hand, for the compiler's
 // sake: their launchers size the launch from these structs and tests/test_layouts.py pins the
@@ -146,6 +140,16 @@ struct CrossLinesLds {
     int* pad = c.take<int>(44);       // (the rest of the launch's 64-int misc block)
     int bytes = c.off;
     GFPL_HD CrossLinesLds(unsigned char* smem, int cap) : c(smem), cap(cap) {}
+};
+
+// ---- k_knn2m<CELL>; the knn table first (see StereoLinesLds), then one chunk of train rows
+struct Knn2Lds {
+    LdsCarver c;
+    int cell;
+    uint32_t* lut = c.take<uint32_t>(knn_lut_dwords(cell));   // at LDS address 0
+    uint32_t* tb = c.take<uint32_t>(KNN_CHUNK * 8);           // train chunk (knn_stage_views, stride KNN_CHUNK)
+    int bytes = c.off;
+    GFPL_HD Knn2Lds(unsigned char* smem, int cell) : c(smem), cell(cell) {}
 };
 
 // ---- k_cross_points<XL>.  XL: the exact projections of the bucketed points in LDS too (bucket

@@ -206,20 +206,6 @@ __global__ void __launch_bounds__(1024, GFPL_CP_WAVES) k_cross_points(KParams p,
     }
 }
 
-template <int CELL>
-__device__ __forceinline__ void knn2_lds(const uint32_t* q, const uint32_t* T, int nt, int& i0, int& d0, int& d1) {
-    int dist0 = 2147483647, dist1 = 2147483647, idx0 = -1;
-    for (int j = 0; j < nt; ++j) {
-        const int d = hamming8<CELL>(q, T + 8 * j);
-        if (d < dist1) {
-            if (dist0 > d) { dist1 = dist0; dist0 = d; idx0 = j; }
-            else { dist1 = d; }
-        }
-    }
-    i0 = idx0; d0 = dist0; d1 = dist1;
-}
-
-
 // dynamic LDS: CrossLinesLds (gfpl_layout.hpp)
 #ifndef GFPL_CL_WAVES
 #define GFPL_CL_WAVES 1
@@ -231,7 +217,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_CL_WAVES) k_cross_lines(KParams p)
     const int cap = p.kl_cap;
     // CrossLinesLds' fields by hand (as k_pose: built from the struct, the compiler schedules this
     // kernel differently and the stage measured 1% slower); tests/test_layouts.py pins the struct, which
-    // the launcher sizes the launch from, to this walk.  knn2_mfma<.., LUT0 = true> below needs the table
+    // the launcher sizes the launch from, to this walk.  knn2_mfma below reads the table
     // at LDS address 0: first in the dynamic LDS, and no static __shared__ in this kernel
     uint32_t* lut = (uint32_t*)smem;
     uint32_t* tb = lut + knn_lut_dwords(1);
@@ -258,7 +244,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_CL_WAVES) k_cross_lines(KParams p)
         __syncthreads();
         // 12: prev queries against curr trains, knn-2 on the matrix cores (gfpl_knn.hpp);
         // 21 (curr queries against prev trains, best index only) from the same distance tiles
-        knn2_mfma<1, true, true, true>(tb, cap, Sc, DP, Sl, (uint32_t*)i12, (uint32_t*)d112, lut, (uint32_t*)i21);
+        knn2_mfma<1>(tb, cap, Sc, DP, Sl, (uint32_t*)i12, (uint32_t*)d112, (uint32_t*)i21);
         __syncthreads();
         for (int i = tid; i < Sl; i += blockDim.x) {
             const uint32_t k0 = (uint32_t)i12[i], k1 = (uint32_t)d112[i];

@@ -1,6 +1,11 @@
-// k_match.hip — the descriptor matchers and match-list statistics StereoFrame exposes to its
-// callers (MapHandler / KeyFrame), beside the knn-2 of k_stereo.hip:
+// k_match.hip — the descriptor matchers over global descriptor sets and the match-list statistics
+// StereoFrame exposes to its callers (MapHandler / KeyFrame):
 //
+//  k_knn2m / k_knn2 : cv::BFMatcher::knnMatch(k = 2) with NORM_HAMMING / NORM_HAMMING2 (ledger T1), one
+//      set against another (gfpl_knn2_hamming, the keyframe matchers) or batched over the sequences
+//      (the initial frame, src/stereoFrame.cpp:183-197).  k_knn2m runs the tiles of gfpl_knn.hpp on
+//      the matrix cores; its packed key holds a 16-bit train index, so above 65536 train rows the
+//      scalar k_knn2 (one thread per query) takes over.
 //  k_radius_count / k_radius_rows : cv::BFMatcher::radiusMatch(NORM_HAMMING[2], maxDistance) as
 //      StereoFrame::matchPointFeatures_radius / matchLineFeatures_radius call it
 //      (src/stereoFrame.cpp:1243-1257): per query row, every train row with distance <= maxDistance
@@ -14,8 +19,140 @@
 //      radix select over order-preserving float keys (NaN above +inf: ledger U12), one workgroup.
 // Keyframe-rate calls (latency, not throughput).
 #include "gfpl_kernels.hpp"
+#include "gfpl_knn.hpp"
 
 namespace gfpl {
+
+// ------------------------------------------------------------------ knn2 --
+// One knn-2 launch.  cap == 0: one set of nq rows against one of nt, results to idx / dist [nq][2].
+// cap > 0 (batched, blockIdx.y = sequence b): rows at q / t + b * cap * 32, counts
+// min(nq_arr[b], cap) / min(nt_arr[b], cap), results (idx0, d0, d1) at packed + b * cap * 6.
+struct Knn2Args {
+    const uint8_t *q, *t;
+    const int *nq_arr, *nt_arr;
+    int nq, nt, cap;
+    int32_t* idx;
+    float* dist;
+    int32_t* packed;
+    __device__ int count_q(int b) const { return nq_arr ? min(nq_arr[b], cap) : nq; }
+    __device__ int count_t(int b) const { return nt_arr ? min(nt_arr[b], cap) : nt; }
+    // query i's neighbours (index -1 and distance INT_MAX where there is none)
+    __device__ void write(int b, int i, int i0, int i1, int d0, int d1) const {
+        if (idx) {
+            idx[2 * i] = i0; idx[2 * i + 1] = i1;
+            dist[2 * i] = (float)d0; dist[2 * i + 1] = (float)d1;
+        }
+        if (packed) {
+            int32_t* o = packed + (size_t)b * cap * 6;
+            o[3 * i] = i0; o[3 * i + 1] = d0; o[3 * i + 2] = d1;
+        }
+    }
+};
+
+// grid (query tiles of 128, sequences); each wave keeps one 32-query column tile in registers
+// while the train rows stream through LDS in chunks of KNN_CHUNK (knn_stage_views) and
+// through the tiles of gfpl_knn.hpp, the chunk's first row c0 added to the keys' train index.
+// dynamic LDS: Knn2Lds (gfpl_layout.hpp), the table at LDS address 0: no static __shared__ here
+template <int CELL>
+__global__ void __launch_bounds__(256) k_knn2m(Knn2Args a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const Knn2Lds L(smem, CELL);
+    const int b = blockIdx.y;
+    const int nq = a.count_q(b), nt = a.count_t(b);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = lane >> 5, c = lane & 31;
+    const int qi = (blockIdx.x * 4 + wave) * 32 + c;
+    if (blockIdx.x * 128 >= nq) return;   // uniform per workgroup
+    const uint8_t* Tg = a.t + (size_t)b * a.cap * 32;
+    knn_lut_fill<CELL>(L.lut);
+    uint32_t qd[8];
+    if (qi < nq) load_desc(a.q + ((size_t)b * a.cap + qi) * 32, qd);
+    else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) qd[i] = 0;
+    }
+    mfma_v4i bq[knn_ksteps<CELL>()];
+#pragma unroll
+    for (int ks = 0; ks < knn_ksteps<CELL>(); ++ks) bq[ks] = knn_frag<CELL, true>(qd, ks, h);
+    const uint32_t offk = knn_query_offk<CELL>(qd);
+    knn_acc_t acc0 = knn_acc_init(0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(acc0[r]));   // (held)
+    const uint32_t* Th = L.tb + 4 * h * KNN_CHUNK;   // this lane half's view
+    uint32_t k0 = 0xFFFFFFFFu, k1 = 0xFFFFFFFFu;
+    for (int c0 = 0; c0 < nt; c0 += KNN_CHUNK) {
+        const int nc = min(KNN_CHUNK, nt - c0);
+        __syncthreads();
+        knn_stage_views<CELL>(L.tb, KNN_CHUNK, Tg + (size_t)c0 * 32, nc);
+        __syncthreads();
+        const int nrt = (nc + 31) >> 5;
+        for (int rt = 0; rt < nrt; ++rt) {
+            const knn_acc_t acc = knn_tile<CELL>(Th, KNN_CHUNK, rt, c, nc, bq, acc0);
+            const uint32_t tb = (uint32_t)(rt * 32 + 4 * h);
+            const uint32_t tko = offk + (uint32_t)c0 + tb;
+            const bool full = rt * 32 + 32 <= nc;   // (wave-uniform)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const uint32_t ro = knn_acc_row(r);
+                uint32_t key = (knn_acc_bits(acc[r]) << 16) + tko + ro;
+                if (!full && (int)(tb + ro) >= nc) key = 0xFFFFFFFFu;
+                knn_top2(k0, k1, key);
+            }
+        }
+    }
+    knn_merge_halves(k0, k1);
+    if (h == 0 && qi < nq) {
+        const bool v0 = k0 != 0xFFFFFFFFu, v1 = k1 != 0xFFFFFFFFu;
+        a.write(b, qi, v0 ? (int)(k0 & 0xFFFFu) : -1, v1 ? (int)(k1 & 0xFFFFu) : -1, v0 ? (int)(k0 >> 16) : 2147483647,
+                v1 ? (int)(k1 >> 16) : 2147483647);
+    }
+}
+
+// one thread per query over the train rows in global memory, the insertion rule of cv::batchDistance
+template <int CELL>
+__global__ void __launch_bounds__(256) k_knn2(Knn2Args a) {
+    const int b = blockIdx.y;
+    const int nq = a.count_q(b), nt = a.count_t(b);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nq) return;
+    const uint8_t* Q = a.q + (size_t)b * a.cap * 32;
+    const uint8_t* T = a.t + (size_t)b * a.cap * 32;
+    uint32_t qd[8];
+    load_desc(Q + (size_t)i * 32, qd);
+    int dist0 = 2147483647, dist1 = 2147483647, idx0 = -1, idx1 = -1;
+    for (int j = 0; j < nt; ++j) {
+        uint32_t td[8];
+        load_desc(T + (size_t)j * 32, td);
+        const int d = hamming8<CELL>(qd, td);
+        if (d < dist1) {
+            if (dist0 > d) { dist1 = dist0; idx1 = idx0; dist0 = d; idx0 = j; }
+            else { dist1 = d; idx1 = j; }
+        }
+    }
+    a.write(b, i, idx0, idx1, dist0, dist1);
+}
+
+// nq_max / nt_max: the largest count of any sequence
+template <int CELL>
+static hipError_t launch_knn2_as(const Knn2Args& a, int nq_max, int nt_max, int B, hipStream_t s) {
+    if (nt_max <= 65536)   // MFMA path: the packed key holds a 16-bit train index
+        hipLaunchKernelGGL(k_knn2m<CELL>, dim3((nq_max + 127) / 128, B), dim3(256), Knn2Lds(nullptr, CELL).bytes, s, a);
+    else
+        hipLaunchKernelGGL(k_knn2<CELL>, dim3((nq_max + 255) / 256, B), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_knn2(const uint8_t* q, int nq, const uint8_t* t, int nt, int cell, int32_t* idx, float* dist,
+                       hipStream_t s) {
+    const Knn2Args a{q, t, nullptr, nullptr, nq, nt, 0, idx, dist, nullptr};
+    return cell == 2 ? launch_knn2_as<2>(a, nq, nt, 1, s) : launch_knn2_as<1>(a, nq, nt, 1, s);
+}
+
+hipError_t launch_knn2_batched(const uint8_t* q, const int* nq, const uint8_t* t, const int* nt, int cap, int B,
+                               int cell, int32_t* packed, hipStream_t s) {
+    const Knn2Args a{q, t, nq, nt, 0, 0, cap, nullptr, nullptr, packed};
+    return cell == 2 ? launch_knn2_as<2>(a, cap, cap, B, s) : launch_knn2_as<1>(a, cap, cap, B, s);
+}
 
 // ---------------------------------------------------------------- radius --
 template <int CELL>

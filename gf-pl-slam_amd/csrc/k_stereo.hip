@@ -3,8 +3,8 @@
 //  k_stereo_points : extractStereoFeatures_ORBSLAM point branch
 //                    (src/stereoFrame.cpp:453-630) + subPixelStereoRefine_ORBSLAM (:340-404)
 //  k_stereo_lines  : extractStereoFeatures_ORBSLAM line branch (src/stereoFrame.cpp:633-767)
-//  k_knn2          : BFMatcher::knnMatch(k=2) NORM_HAMMING / NORM_HAMMING2 (batched)
-//  k_init_points / k_init_lines : extractInitialStereoFeatures (src/stereoFrame.cpp:173-336)
+//  k_init_points / k_init_lines : extractInitialStereoFeatures (src/stereoFrame.cpp:173-336),
+//                    on the batched knn-2 of k_match.hip
 //  k_line_uncertainty : estimateStereoUncertainty on a frame slot
 //
 // One workgroup owns one sequence's frame: the band search, the (dist,iL) sort,
@@ -934,21 +934,6 @@ __device__ void write_line(const KParams& p, DevLines& C, size_t q, const LineOu
     d[0] = s[0]; d[1] = s[1];
 }
 
-// knn-2 of row i of Q against T (both in LDS or global), insertion rule of
-// cv::batchDistance (ledger T1): ties keep the lower train index.
-template <int CELL>
-__device__ __forceinline__ void knn2_row(const uint32_t* q, const uint32_t* T, int nt, int& i0, int& d0, int& d1) {
-    int dist0 = 2147483647, dist1 = 2147483647, idx0 = -1;
-    for (int j = 0; j < nt; ++j) {
-        const int d = hamming8<CELL>(q, T + 8 * j);
-        if (d < dist1) {
-            if (dist0 > d) { dist1 = dist0; dist0 = d; idx0 = j; }
-            else { dist1 = d; }
-        }
-    }
-    i0 = idx0; d0 = dist0; d1 = dist1;
-}
-
 // dynamic LDS: StereoLinesLds (gfpl_layout.hpp); only the train set sits in LDS, so
 // 2000 lines per side (config 5) fit.
 // diagnostic build (-DGFPL_SL_CLOCK): the phase boundaries' wall clock per sequence (scr.dbg): start,
@@ -965,7 +950,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SL_WAVES) k_stereo_lines(KParams p
     const int cap = p.kl_cap;
     // StereoLinesLds' fields by hand (as k_pose: built from the struct, the compiler schedules this
     // kernel differently and the stage measured 1% slower); tests/test_layouts.py pins the struct, which
-    // the launcher sizes the launch from, to this walk.  knn2_mfma<.., LUT0 = true> below needs the table
+    // the launcher sizes the launch from, to this walk.  knn2_mfma below reads the table
     // at LDS address 0: first in the dynamic LDS, and no static __shared__ in this kernel
     uint32_t* lut = (uint32_t*)smem;
     uint32_t* tb = lut + knn_lut_dwords(CELL);
@@ -993,8 +978,8 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SL_WAVES) k_stereo_lines(KParams p
     __syncthreads();
     SL_CLK(1);
     // L->R knn-2 on the matrix cores (gfpl_knn.hpp): keys (dist << 16 | iR); the R->L knn
-    // (only its best index is used) from the same distance tiles (RL)
-    knn2_mfma<CELL, true, true, true>(tb, cap, NR, DLg, NL, (uint32_t*)lr_i, (uint32_t*)lr_d1, lut, (uint32_t*)rl_i);
+    // (only its best index is used) from the same distance tiles
+    knn2_mfma<CELL>(tb, cap, NR, DLg, NL, (uint32_t*)lr_i, (uint32_t*)lr_d1, (uint32_t*)rl_i);
     __syncthreads();
     SL_CLK(2);
     SL_PRIO(1);
@@ -1039,42 +1024,6 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SL_WAVES) k_stereo_lines(KParams p
     }
     if (tid == 0) C.n[b] = off;
     SL_CLK(4);
-}
-
-// ------------------------------------------------------- knn2 (global) --
-// rows of q / t of sequence b at q + b*qstride*32 (counts nq[b], nt[b] or fixed)
-template <int CELL>
-__global__ void __launch_bounds__(256) k_knn2(const uint8_t* q, const int* nq_arr, int nq_fixed, size_t q_stride,
-                                             const uint8_t* t, const int* nt_arr, int nt_fixed, size_t t_stride,
-                                             int cap_clamp, int32_t* out_idx, float* out_dist, int32_t* packed,
-                                             size_t out_stride) {
-    const int b = blockIdx.y;
-    const int nq = nq_arr ? min(nq_arr[b], cap_clamp) : nq_fixed;
-    const int nt = nt_arr ? min(nt_arr[b], cap_clamp) : nt_fixed;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nq) return;
-    const uint8_t* Q = q + (size_t)b * q_stride * 32;
-    const uint8_t* T = t + (size_t)b * t_stride * 32;
-    uint32_t qd[8];
-    load_desc(Q + (size_t)i * 32, qd);
-    int dist0 = 2147483647, dist1 = 2147483647, idx0 = -1, idx1 = -1;
-    for (int j = 0; j < nt; ++j) {
-        uint32_t td[8];
-        load_desc(T + (size_t)j * 32, td);
-        const int d = hamming8<CELL>(qd, td);
-        if (d < dist1) {
-            if (dist0 > d) { dist1 = dist0; idx1 = idx0; dist0 = d; idx0 = j; }
-            else { dist1 = d; idx1 = j; }
-        }
-    }
-    if (out_idx) {
-        out_idx[2 * i] = idx0; out_idx[2 * i + 1] = idx1;
-        out_dist[2 * i] = (float)dist0; out_dist[2 * i + 1] = (float)dist1;
-    }
-    if (packed) {
-        int32_t* o = packed + (size_t)b * out_stride * 3;
-        o[3 * i] = idx0; o[3 * i + 1] = dist0; o[3 * i + 2] = dist1;
-    }
 }
 
 // -------------------------------------------------- initial-frame points --
@@ -1300,17 +1249,12 @@ hipError_t launch_init(const KParams& p, hipStream_t s) {
     // points: knn-2 NORM_HAMMING L->R and R->L into scratch, then gates
     const int cap = p.kp_cap;
     int32_t* lr = p.scr.knn;
-    // MFMA knn (gfpl_knn.hpp): 128 queries per workgroup, train rows streamed through LDS
-    const dim3 gm((cap + 127) / 128, p.B);
-    hipLaunchKernelGGL((k_knn2m<1>), gm, dim3(256), 0, s, p.in.pdesc_l, p.in.n_kp_l, 0, (size_t)cap,
-                       p.in.pdesc_r, p.in.n_kp_r, 0, (size_t)cap, cap, (int32_t*)nullptr, (float*)nullptr,
-                       lr, (size_t)cap * 2);
-    hipLaunchKernelGGL((k_knn2m<1>), gm, dim3(256), 0, s, p.in.pdesc_r, p.in.n_kp_r, 0, (size_t)cap,
-                       p.in.pdesc_l, p.in.n_kp_l, 0, (size_t)cap, cap, (int32_t*)nullptr, (float*)nullptr,
-                       lr + (size_t)cap * 3, (size_t)cap * 2);
+    hipError_t e = launch_knn2_batched(p.in.pdesc_l, p.in.n_kp_l, p.in.pdesc_r, p.in.n_kp_r, cap, p.B, 1, lr, s);
+    if (e != hipSuccess) return e;
+    e = launch_knn2_batched(p.in.pdesc_r, p.in.n_kp_r, p.in.pdesc_l, p.in.n_kp_l, cap, p.B, 1, lr + (size_t)cap * 3, s);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_init_points, dim3(p.B), dim3(512), 0, s, p);
-    const hipError_t e = p.kl_cap > 1024 ? launch_stereo_lines_as<1, true, 1024>(p, s)
-                                         : launch_stereo_lines_as<1, true, 512>(p, s);
+    e = p.kl_cap > 1024 ? launch_stereo_lines_as<1, true, 1024>(p, s) : launch_stereo_lines_as<1, true, 512>(p, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_init_pose, dim3((p.B + 63) / 64), dim3(64), 0, s, p);
     return hipGetLastError();
@@ -1318,28 +1262,6 @@ hipError_t launch_init(const KParams& p, hipStream_t s) {
 
 hipError_t launch_step_bytes(const KParams& p, hipStream_t s) {
     hipLaunchKernelGGL(k_step_bytes, dim3((p.B + 63) / 64), dim3(64), 0, s, p);
-    return hipGetLastError();
-}
-
-hipError_t launch_knn2(const uint8_t* q, int nq, const uint8_t* t, int nt, int cell, int32_t* idx, float* dist,
-                       hipStream_t s) {
-    if (nt <= 65536) {   // MFMA path: the packed key holds a 16-bit train index
-        const dim3 g((nq + 127) / 128, 1);
-        if (cell == 2)
-            hipLaunchKernelGGL((k_knn2m<2>), g, dim3(256), 0, s, q, (const int*)nullptr, nq, (size_t)0, t,
-                               (const int*)nullptr, nt, (size_t)0, 0, idx, dist, (int32_t*)nullptr, (size_t)0);
-        else
-            hipLaunchKernelGGL((k_knn2m<1>), g, dim3(256), 0, s, q, (const int*)nullptr, nq, (size_t)0, t,
-                               (const int*)nullptr, nt, (size_t)0, 0, idx, dist, (int32_t*)nullptr, (size_t)0);
-        return hipGetLastError();
-    }
-    dim3 g((nq + 255) / 256, 1);
-    if (cell == 2)
-        hipLaunchKernelGGL((k_knn2<2>), g, dim3(256), 0, s, q, (const int*)nullptr, nq, (size_t)0, t,
-                           (const int*)nullptr, nt, (size_t)0, 0, idx, dist, (int32_t*)nullptr, (size_t)0);
-    else
-        hipLaunchKernelGGL((k_knn2<1>), g, dim3(256), 0, s, q, (const int*)nullptr, nq, (size_t)0, t,
-                           (const int*)nullptr, nt, (size_t)0, 0, idx, dist, (int32_t*)nullptr, (size_t)0);
     return hipGetLastError();
 }
 

@@ -71,6 +71,15 @@ void cross_lines(int cap) {
     std::printf("}\n");
 }
 
+void knn2(int cell) {
+    const int bytes = Knn2Lds(nullptr, cell).bytes;
+    const Knn2Lds L(buffer(bytes), cell);
+    std::printf("{\"layout\": \"knn2\", \"cell\": %d, \"lut_dwords\": %d, \"chunk\": %d, \"bytes\": %d, \"placed\": %d", cell,
+                knn_lut_dwords(cell), KNN_CHUNK, bytes, L.bytes);
+    F(lut); F(tb);
+    std::printf("}\n");
+}
+
 void cross_points(int cap, int ncell, bool xl) {
     const int bytes = CrossPointsLds(nullptr, cap, ncell, xl).bytes;
     const CrossPointsLds L(buffer(bytes), cap, ncell, xl);
@@ -130,6 +139,7 @@ int main(int argc, char** argv) {
         for (int cell : {1, 2}) stereo_lines(kl, cell);
         cross_lines(kl);
     }
+    for (int cell : {1, 2}) knn2(cell);
     // bucket grids: the smallest, a VGA-sized one and the largest the kernel accepts
     for (int kp : kp_caps)
         for (int ncell : {1, 1200, 2048})

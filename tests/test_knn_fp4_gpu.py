@@ -1,8 +1,9 @@
-"""The MFMA knn-2 (gfpl_knn.hpp, FP4 operands by default) against a numpy brute force.
+"""The MFMA knn-2 (gfpl_knn.hpp, FP4 operands) against a numpy brute force.
 
 gfpl_knn2_hamming (k_knn2m) over every pair of the tile-edge sizes, for NORM_HAMMING (cell 1) and
 NORM_HAMMING2 (cell 2): both indices and both distances must be equal as integers — the FP4 operands
-hold only 0 and +-1 and the f32 accumulator counts exactly, so nothing is approximate.  The in-kernel
+hold only 0 and +-1 and the f32 accumulator counts exactly, so nothing is approximate; and at the
+packed key's last train index, 65535, with the hand-over to the scalar k_knn2 above it.  The in-kernel
 passes (knn2_mfma with its reverse direction, inside k_stereo_lines and k_cross_lines) are compared
 through frameStep with the CPU oracle on the bench workload's shapes here, and on their own, on
 adversarial line descriptors (ties, duplicates, zero rows, tile-edge counts) against numpy, in
@@ -122,6 +123,56 @@ def test_reference_extremes():
         _, _, (ri, rd) = _reference("duplicates", cell, 65, 300)
         assert ri[0].tolist() == [0, 299] and ri[32].tolist() == [31, 32] and ri[1].tolist() == [63, 64]
         assert (rd[[0, 1, 32, 64]] == 0).all()
+
+
+def _top2_blocked(q, t, cell, block=4096):
+    """_top2(_dist(q, t, cell)) for a train set too large for one _dist call (and for a 16-bit index):
+    the distances in row blocks of t, the key with the train index in its low 20 bits."""
+    pop = (_POP1 if cell == 1 else _POP2).astype(np.uint8)
+    D = np.concatenate([pop[q[:, None, :] ^ t[b0:b0 + block][None, :, :]].sum(axis=2, dtype=np.int64)
+                        for b0 in range(0, len(t), block)], axis=1)
+    key = np.sort((D << 20) + np.arange(len(t), dtype=np.int64)[None, :], axis=1)[:, :2]
+    return (key & 0xFFFFF).astype(np.int32), (key >> 20).astype(np.float32)
+
+
+@pytest.mark.parametrize("cell", [1, 2])
+@pytest.mark.parametrize("nt", [65536, 65537])
+def test_knn2_hamming_index_boundary(ctx, nt, cell):
+    """The packed key's 16-bit train index at its last value, and the hand-over to the scalar kernel:
+    nt = 65536 is the largest set the MFMA kernel takes (train row 65535 sits in the last tile of the
+    last chunk), nt = 65537 the smallest that goes to k_knn2.  Random descriptors with planted rows at
+    distance 0: set 0 has q[0] = t[nt - 1] and q[32] = t[65535]; set 1 also has t[nt - 1] = t[0] and
+    q[1] = t[0], so the tie goes to index 0 and the second neighbour is nt - 1 at distance 0.  The
+    planted answers are asserted on the brute force itself."""
+    import torch
+    nq = 33
+    rng = np.random.default_rng(77 + cell)
+    q0 = rng.integers(0, 256, (nq, 32), dtype=np.uint8)
+    t0 = rng.integers(0, 256, (nt, 32), dtype=np.uint8)
+    for dup in (0, 1):
+        q, t = q0.copy(), t0.copy()
+        if dup:
+            t[nt - 1] = t[0]
+            q[1] = t[0]
+        q[0] = t[nt - 1]
+        q[32] = t[65535]
+        ri, rd = _top2_blocked(q, t, cell)
+        assert rd[0, 0] == 0 and rd[32, 0] == 0
+        if dup:
+            assert ri[1].tolist() == [0, nt - 1] and rd[1].tolist() == [0, 0]
+            assert ri[0].tolist() == [0, nt - 1] and rd[0].tolist() == [0, 0]
+            assert ri[32, 0] == (0 if nt == 65536 else 65535)
+        else:
+            assert ri[0, 0] == nt - 1 and ri[32, 0] == 65535 and rd[0, 1] > 0
+        qd, td = torch.from_numpy(q).cuda(), torch.from_numpy(t).cuda()
+        idx = torch.full((nq, 2), -7, dtype=torch.int32, device="cuda")
+        dist = torch.full((nq, 2), -7.0, dtype=torch.float32, device="cuda")
+        assert ctx.knn2(qd, nq, td, nt, cell, idx, dist) == 0
+        ctx.synchronize()
+        gi, gd = idx.cpu().numpy(), dist.cpu().numpy()
+        w = np.nonzero((gi != ri).any(axis=1) | (gd != rd).any(axis=1))[0]
+        assert len(w) == 0, (f"nt {nt} cell {cell} set {dup}: {len(w)} queries differ, first q {w[0]}: got "
+                             f"{gi[w[0]].tolist()} {gd[w[0]].tolist()} want {ri[w[0]].tolist()} {rd[w[0]].tolist()}")
 
 
 @pytest.mark.parametrize("wide", ["0", "4096"])

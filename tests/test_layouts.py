@@ -19,9 +19,9 @@ KP_CAPS = {2, 66, 2000, 2048, 2050, 8192}
 KL_CAPS = {2, 34, 200, 500, 1024, 1026, 2048}
 HEIGHTS = sorted({c["height"] for c in gfpl.CAMERAS.values()})
 LEVELS = (4, 8)
-# the expansion table of the knn MFMA, FP4 operands (the build's default): dwords per cell size
+# the expansion table of the knn MFMA (FP4 operands): dwords per cell size
 LUT = {1: 256 * 1, 2: 256 * 2}
-SP_CHUNK, SP_MINR_PAD, CH_STRIDE, LSD_RING = 32, 32, 66, 256
+SP_CHUNK, SP_MINR_PAD, CH_STRIDE, LSD_RING, KNN_CHUNK = 32, 32, 66, 256, 1024
 
 
 @pytest.fixture(scope="module")
@@ -85,7 +85,7 @@ def test_stereo_lines(rows):
         cap = r["kl_cap"]
         # stereo_lines_lds(): the table of CELL 2, the larger one, for both instantiations
         assert r["bytes"] == cap * 32 + cap * 16 + 260 * 4 + 64 * 4 + LUT[2] * 4, r
-        assert r["lut"] == 0, "knn2_mfma<LUT0> reads the table at LDS address 0"
+        assert r["lut"] == 0, "knn2_mfma reads the table at LDS address 0"
         tb = LUT[r["cell"]] * 4
         lr_i = tb + cap * 32
         misc = lr_i + 4 * cap * 4 + 260 * 4
@@ -101,7 +101,7 @@ def test_cross_lines(rows):
     for r in got:
         cap = r["kl_cap"]
         assert r["bytes"] == cap * 32 + cap * 16 + 520 * 4 + 64 * 4 + LUT[1] * 4, r
-        assert r["lut"] == 0, "knn2_mfma<LUT0> reads the table at LDS address 0"
+        assert r["lut"] == 0, "knn2_mfma reads the table at LDS address 0"
         tb = LUT[1] * 4
         i12 = tb + cap * 32
         h12 = i12 + cap * 16
@@ -109,6 +109,18 @@ def test_cross_lines(rows):
         assert (r["tb"], r["i12"], r["d012"], r["d112"], r["i21"], r["h12"], r["h0"]) == \
             (tb, i12, i12 + cap * 4, i12 + cap * 8, i12 + cap * 12, h12, h12 + 260 * 4), r
         assert r["scan"] == misc and r["th"] == misc + 16 * 4, r
+
+
+def test_knn2(rows):
+    got = of(rows, "knn2")
+    assert {r["cell"] for r in got} == {1, 2}
+    for r in got:
+        assert r["lut_dwords"] == LUT[r["cell"]] and r["chunk"] == KNN_CHUNK, r
+        assert r["lut"] == 0, "knn_tile reads the table at LDS address 0"
+        assert r["tb"] == 4 * LUT[r["cell"]], r
+        # launch_knn2_as: the table, then one chunk of train rows as views (8 dwords a row), packed
+        assert r["bytes"] == 4 * (LUT[r["cell"]] + 8 * KNN_CHUNK), r
+        assert r["bytes"] <= 64 * 1024, "k_knn2m launches without raising the dynamic-LDS ceiling"
 
 
 def test_cross_points(rows):

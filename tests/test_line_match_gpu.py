@@ -1,6 +1,6 @@
 """k_stereo_lines (both cells) and k_cross_lines on hand-made line descriptors, against plain numpy.
 
-The kernels' knn pass (knn2_mfma<CELL, true, true, true>, gfpl_knn.hpp: train views, table reads at
+The kernels' knn pass (knn2_mfma<CELL>, gfpl_knn.hpp: train views, table reads at
 LDS address 0, the accumulator block kept across tiles, top-2 by v_med3_u32, the reverse direction by a
 DPP reduce-scatter and one atomicMin per lane, masked partial tiles) is otherwise reached only through
 frameStep on synthetic frames, whose descriptors never tie, never repeat, are never zero and land on a
