@@ -278,8 +278,12 @@ int in_release(gfpl_seqbatch* sb, const gfpl_frames* in, int slot) {
     return GFPL_OK;
 }
 
+// the proof mode a line cut runs with: the min-eigenvalue search (cut_with_max_vol = 0) evaluates every
+// step with the reference's arithmetic and has nothing to prove
+static int cut_mode(const gfpl_config& c) { return c.cut_with_max_vol ? c.cut_proof : 0; }
+
 int cfg_supported(const gfpl_config& c) {
-    if (!c.best_lr_matches || !c.lr_in_parallel || !c.cut_with_max_vol) return GFPL_E_UNSUPPORTED;
+    if (!c.best_lr_matches || !c.lr_in_parallel) return GFPL_E_UNSUPPORTED;
     if (c.max_point_match_num < 1 || c.max_point_match_num > GFPL_MAX_MATCHED_PT) return GFPL_E_INVALID;
     if (c.max_line_match_num < 1 || c.max_line_match_num > GFPL_MAX_MATCHED_LS) return GFPL_E_INVALID;
     // the certified cut search needs a margin far above its ~1e-13 error
@@ -563,7 +567,7 @@ int gfpl_cross_lines(gfpl_seqbatch* sb) {
 int gfpl_line_cut(gfpl_seqbatch* sb) {
     if (!sb) return GFPL_E_INVALID;
     if (!sb->initialized || !sb->has_curr) return GFPL_E_STATE;
-    sb->last_cut_mode = sb->ctx->cfg.cut_proof;
+    sb->last_cut_mode = cut_mode(sb->ctx->cfg);
     HIPCHK(launch_line_cut(params(sb, nullptr), sb->ctx->stream, nullptr));
     return GFPL_OK;
 }
@@ -588,7 +592,7 @@ int gfpl_insert_stereo_pair(gfpl_seqbatch* sb, const gfpl_frames* in) {
     tmark(c, 3);
     HIPCHK(launch_cross_lines(p, c->stream));
     tmark(c, 4);
-    sb->last_cut_mode = c->cfg.use_line_conf_cut ? c->cfg.cut_proof : -1;
+    sb->last_cut_mode = c->cfg.use_line_conf_cut ? cut_mode(c->cfg) : -1;
     if (c->cfg.use_line_conf_cut)
         HIPCHK(launch_line_cut(p, c->stream, c->timing ? &c->ev[7] : nullptr));
     HIPCHK(launch_step_bytes(p, c->stream));

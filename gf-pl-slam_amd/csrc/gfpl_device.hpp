@@ -660,8 +660,9 @@ GFPL_DEV double kf_entropy(const double* cov) {
 }
 
 // SelfAdjointEigenSolver eigenvalues -> cyclic Jacobi, ascending (see oracle eig_sym)
-template <int N>
-GFPL_DEV void eig_sym(const double* A, double* w) {
+// COUNT: *sweeps += the sweeps that rotated (k_cut_search_eig's counter; the values are the same)
+template <int N, bool COUNT = false>
+GFPL_DEV void eig_sym(const double* A, double* w, int* sweeps = nullptr) {
     double a[N * N];
 #pragma unroll
     for (int i = 0; i < N * N; ++i) a[i] = A[i];
@@ -688,6 +689,7 @@ GFPL_DEV void eig_sym(const double* A, double* w) {
             }
             if (fin && off < thr) break;
         }
+        if (COUNT) ++*sweeps;
 #pragma unroll
         for (int p = 0; p < N - 1; ++p)
 #pragma unroll

@@ -12,6 +12,8 @@
 //               of every chain per wave iteration (see the comment at the kernel);
 //  k_cut_finish (parallel) full 6x6 info of the chosen ratio (invCovPose) and
 //               the cut endpoints of every matched line.
+// With cut_with_max_vol = 0 the metric is getMinEigenValue(invCov_sum) (:1671-1678, 1712-1719) and
+// k_cut_search_eig takes k_cut_search's place (every step in the reference's arithmetic).
 // Only the lower triangle is carried through the search: LLT reads nothing
 // else (ledger Q11).
 #include <cstdlib>
@@ -2150,6 +2152,178 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
 }
 
+// ------------------------------------------------- min-eigenvalue search --
+// cut_with_max_vol = 0 (src/stereoFrameHandler.cpp:1671-1678, 1712-1719; ledger N5): the same greedy
+// search with getMinEigenValue(invCov_sum) as its metric, pinned to element 0 of eig_sym<6> of the
+// matrix whose lower triangle is that of info + invCov_sum, mirrored.  A smallest eigenvalue has no
+// determinant lemma, so every step is the reference's arithmetic and nothing of the margined search
+// is used: no comparison record, no bounds, no ratio keys, no progress exchange, no prefetch.
+// Eight lanes per sequence, eight sequences per wave.  A wave iteration is one round of every group:
+//  * a step round: lane j evaluates neighbour j — both cut endpoints in reference order, the
+//    assembled info (kept in LDS for the line's finalisation), + S from LDS (the exact running sum
+//    minus the line's r = 0 info), eig_sym<6> — and the group decides with group_first_max;
+//  * an open round (a line's first): every lane evaluates the running sum itself, the centre
+//    metric of the line's first step (:1678).
+// Lane j owns entries j, j + 8, j + 16 of the running sum, of S and of the candidate's info in
+// registers, and publishes the matrix the next round reads in LDS.  Groups whose sequence is done
+// (or empty) are masked out of every round.
+#define CUTE_LN 27   // line data row: sP 0, eP 3, covS 6, covE 15, Jl 24 (26 used; odd strides: the
+                     // 8 groups' rows start in different banks)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_cut_search_eig(KParams p) {
+    __shared__ double lnd[CUT_G][CUTE_LN];       // the current line
+    __shared__ double dti[CUT_G][17];            // DT_inv
+    __shared__ double smat[CUT_G][21];           // open round: invCov_sum; step rounds: S
+    __shared__ double ninf[CUT_G][8 * 21 + 1];   // neighbour j's info of this round
+    const int lane = threadIdx.x;
+    const int g = lane >> 3, j = lane & 7;
+    const int b = blockIdx.x * CUT_G + g;
+    const bool seq = b < p.B;
+    const int nls = seq ? p.tr.n_matched_ls[b] : 0;
+    const DevCam& cam = p.cam;
+    const double homog = p.cfg.homog_th;
+    DevLines& L = p.prev.ls;
+    const size_t lb = (size_t)(seq ? b : 0) * p.kl_cap;
+    const int32_t* mls = p.tr.matched_ls + (size_t)(seq ? b : 0) * p.mls_cap;
+    const double* rec_l = p.scr.cut_rec + (size_t)(seq ? b : 0) * p.mls_cap * CUT_REC;
+    const double st = p.cfg.cut_step;
+    const double rlo = p.cfg.cut_rng[0], rhi = p.cfg.cut_rng[1];
+    const double nb0 = nb_step(j, 0, st), nb1 = nb_step(j, 1, st);
+    // group state (identical in the 8 lanes of a group)
+    int m = 0;
+    int open = 1;        // the next round evaluates the centre metric of the line's first step
+    double r0 = 0.0, r1 = 0.0;
+    double mc = 0.0;     // centre metric
+    size_t q_cur = 0;
+    // lane state: entries j + 8 kk of invCov_sum (se), of S (ss) and of the line's info (ci: r = 0, then
+    // the accepted candidate's — L.invCov of the reference)
+    double se[3] = {0.0, 0.0, 0.0}, ss[3] = {0.0, 0.0, 0.0}, ci[3] = {0.0, 0.0, 0.0};
+    int n_steps = 0, n_eval = 0, n_sweeps = 0;
+    // line m opens: its data, S = invCov_sum - its r = 0 info (k_cut_prep's record), invCov_sum published
+    auto open_line = [&]() {
+        q_cur = lb + mls[m];
+        for (int i = j; i < 26; i += 8) {
+            double v;
+            if (i < 3) v = L.sP[3 * q_cur + i];
+            else if (i < 6) v = L.eP[3 * q_cur + i - 3];
+            else if (i < 15) v = L.covS[9 * q_cur + i - 6];
+            else if (i < 24) v = L.covE[9 * q_cur + i - 15];
+            else v = L.le_obs[3 * q_cur + i - 24];
+            lnd[g][i] = v;
+        }
+#pragma unroll
+        for (int kk = 0; kk < 3; ++kk) {
+            const int e = j + 8 * kk;
+            if (e < 21) {
+                ci[kk] = rec_l[(size_t)m * CUT_REC + CUT_FAST + e];
+                ss[kk] = se[kk] - ci[kk];
+                smat[g][e] = se[kk];
+            }
+        }
+        r0 = 0.0;
+        r1 = 0.0;
+        open = 1;
+    };
+    if (nls > 0) {
+        for (int i = j; i < 16; i += 8) dti[g][i] = p.scr.cut_dtinv[16 * (size_t)b + i];
+#pragma unroll
+        for (int kk = 0; kk < 3; ++kk) {
+            const int e = j + 8 * kk;
+            if (e < 21) se[kk] = p.scr.cut_sum[24 * (size_t)b + e];
+        }
+        open_line();
+    }
+    while (__any(m < nls)) {   // wave-uniform loop; groups that are done idle
+        wave_lds_sync();
+        const bool live = m < nls;
+        const double t0 = r0 + nb0, t1 = r1 + nb1;
+        int valid = (live && !open) ? 1 : 0;
+        if (t0 + t1 > 1.0) valid = 0;
+        if (t0 < rlo || t0 > rhi) valid = 0;
+        if (t1 < rlo || t1 > rhi) valid = 0;
+        double v = 0.0;
+        if (live && (open || valid)) {
+            double tot[21];
+            if (open) {
+#pragma unroll
+                for (int e = 0; e < 21; ++e) tot[e] = smat[g][e];
+            } else {
+                double S7[7], E7[7], info[21];
+                const double* d = lnd[g];
+                cut_endpoint(cam, homog, dti[g], d + 24, d, d + 3, d + 6, d + 15, t0, S7);
+                cut_endpoint(cam, homog, dti[g], d + 24, d + 3, d, d + 15, d + 6, t1, E7);
+                cut_assemble<false>(S7, E7, info);
+#pragma unroll
+                for (int e = 0; e < 21; ++e) {
+                    ninf[g][21 * j + e] = info[e];
+                    tot[e] = info[e] + smat[g][e];
+                }
+            }
+            double A[36], w[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+                for (int k = 0; k <= i; ++k) {
+                    A[i * 6 + k] = tot[tri(i, k)];
+                    A[k * 6 + i] = tot[tri(i, k)];
+                }
+            int sw = 0;
+            eig_sym<6, true>(A, w, &sw);
+            v = w[0];
+            if (!open || j == 0) {   // (an open round's eight evaluations are one, counted once)
+                n_sweeps += sw;
+                ++n_eval;
+            }
+        }
+        wave_lds_sync();
+        double top;
+        const int best = group_first_max(v, valid, j, mc, top);
+        if (live && open) {   // the centre of the first step; S replaces invCov_sum in LDS
+            mc = v;
+            open = 0;
+#pragma unroll
+            for (int kk = 0; kk < 3; ++kk) {
+                const int e = j + 8 * kk;
+                if (e < 21) smat[g][e] = ss[kk];
+            }
+        } else if (live) {
+            ++n_steps;
+            bool fin = true;
+            if (best >= 0) {
+#pragma unroll
+                for (int kk = 0; kk < 3; ++kk) {
+                    const int e = j + 8 * kk;
+                    if (e < 21) ci[kk] = ninf[g][21 * best + e];
+                }
+                r0 = r0 + nb_step(best, 0, st);
+                r1 = r1 + nb_step(best, 1, st);
+                mc = top;
+                fin = !(r0 + r1 <= 1.0);   // while-condition
+            }
+            if (fin) {
+                if (j == 0) {
+                    L.cut[2 * q_cur] = r0;
+                    L.cut[2 * q_cur + 1] = r1;
+                }
+#pragma unroll
+                for (int kk = 0; kk < 3; ++kk) se[kk] = ss[kk] + ci[kk];
+                ++m;
+                if (m < nls) open_line();
+            }
+        }
+    }
+    // the sequence's counters: steps (all of them exact), no line without a bound; debug slots 0 / 1:
+    // Jacobi sweeps that rotated and metric evaluations, summed over the group's lanes
+    n_sweeps += __shfl_xor(n_sweeps, 1); n_sweeps += __shfl_xor(n_sweeps, 2); n_sweeps += __shfl_xor(n_sweeps, 4);
+    n_eval += __shfl_xor(n_eval, 1); n_eval += __shfl_xor(n_eval, 2); n_eval += __shfl_xor(n_eval, 4);
+    if (seq && j == 0) {
+        p.scr.bytes[(size_t)STEP_REC * b + 16] = n_steps;
+        p.scr.bytes[(size_t)STEP_REC * b + 17] = n_steps;
+        p.scr.bytes[(size_t)STEP_REC * b + 19] = 0;
+        p.scr.dbg[8 * (size_t)b + 0] = n_sweeps;
+        p.scr.dbg[8 * (size_t)b + 1] = n_eval;
+    }
+}
+
 // ---------------------------------------------------------------- finish --
 // invCovPose of the chosen ratio + updateEndPointByRatio (ledger Q4)
 #ifndef GFPL_FIN_WAVES
@@ -2161,7 +2335,9 @@ __global__ void __launch_bounds__(64, GFPL_FIN_WAVES) k_cut_finish(KParams p) {
     // proven mode (cut_proof 1 / 3): k_cut_verify wrote the proven sequences' invCovPose, this kernel their
     // cut endpoints; the redone ones get both here
     if (nls == 0) return;
-    const bool ends_only = (p.cfg.cut_proof == 1 || p.cfg.cut_proof == 3) && p.scr.cut_flag[b] == 0;
+    // (the min-eigenvalue search, cut_with_max_vol = 0, ignores cut_proof: everything is done here)
+    const bool ends_only = p.cfg.cut_with_max_vol && (p.cfg.cut_proof == 1 || p.cfg.cut_proof == 3) &&
+                           p.scr.cut_flag[b] == 0;
     const DevCam& cam = p.cam;
     DevLines& L = p.prev.ls;
     const size_t lb = (size_t)b * p.kl_cap;
@@ -3038,6 +3214,13 @@ hipError_t launch_line_cut(const KParams& p, hipStream_t s, const hipEvent_t* ma
         hipLaunchKernelGGL(k_cut_prep<8>, dim3(p.B), dim3(512), cut_prep_lds(8), s, p);
     } else {
         hipLaunchKernelGGL(k_cut_prep<1>, dim3(p.B), dim3(64), cut_prep_lds(1), s, p);
+    }
+    if (!p.cfg.cut_with_max_vol) {   // min-eigenvalue metric: every step exact, cut_certify / cut_proof unused
+        if (marks) (void)hipEventRecord(marks[0], s);
+        hipLaunchKernelGGL(k_cut_search_eig, gsearch, dim3(64), 0, s, p);
+        if (marks) (void)hipEventRecord(marks[1], s);
+        hipLaunchKernelGGL(k_cut_finish, dim3(p.B), dim3(64), 0, s, p);
+        return hipGetLastError();
     }
     if (mode == 2) {   // the per-line operand error bounds the eager agreement bound starts from
         hipLaunchKernelGGL(k_cut_bounds, dim3((p.mls_cap + 63) / 64, p.B), dim3(64), 0, s, p);

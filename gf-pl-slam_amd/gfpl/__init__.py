@@ -807,7 +807,8 @@ class Context:
         return out
 
     def kernel_times(self) -> np.ndarray:
-        """[k_cut_prep, k_cut_search, k_cut_finish, k_pose] device ms of the last step."""
+        """[k_cut_prep, k_cut_search (k_cut_search_eig with cut_with_max_vol = 0), k_cut_finish, k_pose]
+        device ms of the last step."""
         out = np.zeros(4, np.float32)
         check(self.L.gfpl_get_kernel_times(self.h, out.ctypes.data), "kernel_times")
         return out
@@ -1080,7 +1081,8 @@ class StereoFrameHandler:
 
     def debug_clocks(self) -> np.ndarray:
         """gfpl_debug_clocks: per-sequence debug slots [B][8] (int64): the instrumented builds' clocks;
-        in the product build slots 6 / 7 hold the measured-mode line-cut wave's HW_ID / XCC_ID."""
+        in the product build slots 6 / 7 hold the measured-mode line-cut wave's HW_ID / XCC_ID, and with
+        cut_with_max_vol = 0 slots 0 / 1 the search's Jacobi sweeps that rotated / metric evaluations."""
         out = np.zeros((self.B, 8), np.int64)
         check(self.L.gfpl_debug_clocks(self.h, out.ctypes.data), "debug_clocks")
         return out

@@ -5,8 +5,10 @@
 // idx, ts) signature) or on synthetic stereo detections (gfpl_synth).
 //
 //   plslam_gpu [--camera vga|euroc|kitti|stress] [--frames N] [--seq S] [--out PREFIX] [--json]
-//              [--images DIR] [--orb-features N] [--rectify FILE]
+//              [--images DIR] [--orb-features N] [--rectify FILE] [--min-eig-cut]
 //
+// --min-eig-cut sets Config::cutWithMaxVol() = false: the line cut maximises the smallest eigenvalue
+// of invCov_sum instead of its logdet (src/stereoFrameHandler.cpp:1671-1678).
 // --images DIR reads DIR/left/%06d.pgm and DIR/right/%06d.pgm (binary 8-bit PGM of the
 // camera's size; the reference's app reads its dataset through cv::imread) for frames
 // 0..N-1 (stopping at the first missing pair) and the time stamps from DIR/times.txt
@@ -161,6 +163,7 @@ static int run(int argc, char** argv) {
         else if (a == "--images") images = next();
         else if (a == "--orb-features") orb_features = std::stoi(next());
         else if (a == "--rectify") rectify = next();
+        else if (a == "--min-eig-cut") Config::cutWithMaxVol() = false;   // the line cut's max-min-eig metric
         else { std::cerr << "unknown option " << a << "\n"; return 2; }
     }
     const CamDef* cd = nullptr;

@@ -86,7 +86,9 @@ typedef struct gfpl_config {
     int    best_lr_matches;      /* :81  true  (only true is implemented)      */
     int    lr_in_parallel;       /* :79  true  (radius branch of cross points) */
     int    use_line_conf_cut;    /* :83  true                                   */
-    int    cut_with_max_vol;     /* :86  true  (only true is implemented)      */
+    int    cut_with_max_vol;     /* :86  true: the line cut's metric is logdet(invCov_sum);
+                                    0: getMinEigenValue(invCov_sum) (k_cut_search_eig, DESIGN.md §3
+                                    N5): every step exact, cut_certify / cut_proof are ignored   */
     double ratio_disp_std;       /* :84  0.15                                   */
     double ratio_disp_std_hor;   /* :85  0.9                                    */
     int    max_line_match_num;   /* :94  300                                    */
