@@ -1200,6 +1200,11 @@ int gfpl_write_track(gfpl_seqbatch* sb, int seq, const gfpl_track_host* o) {
     if (!sb || !o || seq < 0 || seq >= sb->B) return GFPL_E_INVALID;
     if (o->n_matched_pt < 0 || o->n_matched_pt > sb->mpt_cap || o->n_matched_ls < 0 || o->n_matched_ls > sb->mls_cap)
         return GFPL_E_CAPACITY;
+    // k_pose and the line cut gather prev-frame records by these indices: none may leave the frame's slot
+    for (int i = 0; i < o->n_matched_pt; ++i)
+        if (o->matched_pt[i] < 0 || o->matched_pt[i] >= sb->kp_cap) return GFPL_E_INVALID;
+    for (int i = 0; i < o->n_matched_ls; ++i)
+        if (o->matched_ls[i] < 0 || o->matched_ls[i] >= sb->kl_cap) return GFPL_E_INVALID;
     hipStream_t s = sb->ctx->stream;
     XFER(h2d, sb->tr.n_matched_pt + seq, &o->n_matched_pt, 1);
     XFER(h2d, sb->tr.n_matched_ls + seq, &o->n_matched_ls, 1);

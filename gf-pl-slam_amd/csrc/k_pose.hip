@@ -362,6 +362,8 @@ __device__ void gauss_newton(const KParams& p, const PoseCtx& X, PoseLDS& S, dou
             }
         }
         if (W > 1 && lane == 0) { S.pcomp = cpts ? 1 : 0; S.lcomp = clns ? 1 : 0; }
+        // a run of no iterations leaves H = 0 (the oracle's pin of the reference's uninitialised H, Q13a)
+        if (lane < 36) S.H[lane] = 0.0;
         pose_bar<W>();
     }
     const double* pa = cpts ? X.pact : X.pin;

@@ -699,6 +699,9 @@ int  gfpl_read_frame(gfpl_seqbatch* sb, int which, int seq, gfpl_frame_host* out
  * simulators build frames through the public members (src/simulate_line_cut.cpp:62-212). */
 int  gfpl_write_frame(gfpl_seqbatch* sb, int which, int seq, const gfpl_frame_host* in);
 int  gfpl_read_track(gfpl_seqbatch* sb, int seq, gfpl_track_host* out);
+/* GFPL_E_CAPACITY for a list longer than the seqbatch's match budget, GFPL_E_INVALID for a matched
+ * index outside [0, kp_cap) / [0, kl_cap) (the pose solver and the line cut gather prev-frame
+ * records by these indices); checked on the host before anything is copied.                  */
 int  gfpl_write_track(gfpl_seqbatch* sb, int seq, const gfpl_track_host* in);
 /* The track of the step before the last gfpl_update_frame / gfpl_frame_step: the
  * matched lists it cleared (matched_pt.clear(), src/stereoFrameHandler.cpp:889-890)

@@ -22,6 +22,21 @@ def bitwise_equal(a: np.ndarray, b: np.ndarray) -> bool:
     return a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
+def bitwise_equal_nan(a: np.ndarray, b: np.ndarray) -> bool:
+    """bitwise_equal, except that a NaN matches a NaN at the same position whatever its sign and payload
+    (the default NaNs of x86 and gfx950 differ in the sign bit)."""
+    a = np.ascontiguousarray(a); b = np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if a.dtype.kind != "f":
+        return a.tobytes() == b.tobytes()
+    na, nb = np.isnan(a), np.isnan(b)
+    if not np.array_equal(na, nb):
+        return False
+    u = np.dtype(f"u{a.dtype.itemsize}")
+    return np.array_equal(a.view(u)[~na], b.view(u)[~nb])
+
+
 def diff_fields(g, o, names, rows=None, what=""):
     """Return list of mismatching field descriptions (bit-exact)."""
     bad = []
