@@ -253,7 +253,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_CL_WAVES) k_cross_lines(KParams p)
             atomicAdd(&h12[d1 - d0], 1);
             atomicAdd(&h0[d0], 1);
         }
-        for (int j = tid; j < Sc; j += blockDim.x) i21[j] = (int)((uint32_t)i21[j] & 0xFFFFu);
+        for (int j = tid; j < Sc; j += blockDim.x) i21[j] = (int)((uint32_t)i21[j] & KNN_IDX_MASK);
         __syncthreads();
         if (tid < 128) {   // (waves 0 and 1: the two medians side by side)
             if (tid < 64) {

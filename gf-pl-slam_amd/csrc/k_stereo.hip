@@ -989,7 +989,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SL_WAVES) k_stereo_lines(KParams p
         lr_i[i] = (int)(k0 & 0xFFFFu); lr_d0[i] = d0; lr_d1[i] = d1;
         atomicAdd(&hist[d1 - d0], 1);   // lineDescriptorMAD deviations |d1-d0| (U1 pin)
     }
-    for (int j = tid; j < NR; j += blockDim.x) rl_i[j] = (int)((uint32_t)rl_i[j] & 0xFFFFu);
+    for (int j = tid; j < NR; j += blockDim.x) rl_i[j] = (int)((uint32_t)rl_i[j] & KNN_IDX_MASK);
     __syncthreads();
     if (tid < 64) {   // (wave 0)
         const int v = wave_hist_rank(hist, NL / 2, 257);
