@@ -90,10 +90,7 @@ namespace {
         }                                                           \
     } while (0)
 
-int debug_fill_byte() {
-    const char* e = getenv("GFPL_DEBUG_FILL");
-    return e ? (int)(strtol(e, nullptr, 0) & 0xFF) : 0;
-}
+int debug_fill_byte() { return env_int("GFPL_DEBUG_FILL", 0) & 0xFF; }
 
 // Every field of a frame slot, once, in layout order: device member, host member
 // (gfpl_frame_host) and elements per feature.  v.pt / v.ls: a row per point / per line;
@@ -157,7 +154,7 @@ void carve(Carver& c, gfpl_seqbatch* sb) {
     sb->scr.proj = reinterpret_cast<double*>(sb->scr.knn);
     sb->scr.bytes = c.take<int64_t>(B * STEP_REC);
     sb->scr.n_subpix = c.take<int32_t>(B);
-    sb->scr.cut_sum = c.take<double>(B * 24);
+    sb->scr.cut_sum = c.take<double>(B * CUT_SUM_REC);
     sb->scr.cut_dtinv = c.take<double>(B * 16);
     sb->scr.cut_vtab = c.take<double>(B * sb->mls_cap * 2 * CUT_KS);
     sb->scr.pose_DT = c.take<double>(B * 16);
@@ -168,14 +165,14 @@ void carve(Carver& c, gfpl_seqbatch* sb) {
     sb->scr.pose_act = c.take<double>(B * (6 * (size_t)sb->mpt_cap + 10 * (size_t)sb->mls_cap));
     sb->scr.pose_dtini = c.take<double>(B * 16);
     sb->scr.cross_tinv = c.take<double>(B * 16);
-    sb->scr.dbg = c.take<int64_t>(B * 8);
+    sb->scr.dbg = c.take<int64_t>(B * DBG_REC);
     sb->scr.cut_prog = c.take<int32_t>((size_t)1 << 17);
     sb->scr.cut_path = c.take<uint8_t>(B * sb->mls_cap * CUT_PATH);
     sb->scr.cut_flag = c.take<int32_t>(B);
     sb->scr.cut_vmax = c.take<double>(B * sb->mls_cap * CUT_VMAX);
     sb->scr.cut_offl = c.take<int32_t>(1 + B * sb->mls_cap);
     sb->scr.cut_dtln = c.take<int32_t>(1 + CUT_DTL * B);
-    sb->scr.cut_dtl = c.take<double>(CUT_DTL * B * 32);
+    sb->scr.cut_dtl = c.take<double>(CUT_DTL * B * CUT_DTL_REC);
     sb->scr.kf_mask = c.take<int32_t>(B);
     sb->last_n_pt = c.take<int32_t>(B);
     sb->last_n_ls = c.take<int32_t>(B);
@@ -1248,7 +1245,7 @@ int gfpl_get_kernel_times(gfpl_ctx* c, float* ms4) {
 }  // extern "C"
 
 namespace {
-// column sums over the B per-sequence step records (k_step_bytes)
+// column sums over the B per-sequence step records (gfpl_records.hpp), all STEP_REC slots
 int step_rec_sums(gfpl_seqbatch* sb, int64_t* sums) {
     std::vector<int64_t> v((size_t)sb->B * STEP_REC);
     HIPCHK(hipStreamSynchronize(sb->ctx->stream));
@@ -1258,6 +1255,15 @@ int step_rec_sums(gfpl_seqbatch* sb, int64_t* sums) {
         for (int b = 0; b < sb->B; ++b) t += v[(size_t)b * STEP_REC + s];
         sums[s] = t;
     }
+    return GFPL_OK;
+}
+// ... of the n slots from `first` (zeros instead when !on)
+int step_rec_sums(gfpl_seqbatch* sb, int first, int n, int64_t* out, bool on = true) {
+    if (!sb || !out) return GFPL_E_INVALID;
+    int64_t v[STEP_REC];
+    const int e = step_rec_sums(sb, v);
+    if (e) return e;
+    for (int s = 0; s < n; ++s) out[s] = on ? v[first + s] : 0;
     return GFPL_OK;
 }
 }  // namespace
@@ -1270,56 +1276,36 @@ int gfpl_last_step_kernel_bytes(gfpl_seqbatch* sb, int64_t* bytes4) {
     int e = step_rec_sums(sb, v);
     if (e) return e;
     // k_cut_search bytes are recorded per sequence; k_pose's are the pose stage's.  k_cut_prep and
-    // k_cut_finish from the summed matched counts (v[13] M_p, v[14] M_l):
+    // k_cut_finish from the summed matched counts M_p, M_l:
     //   prep:   per matched line its cut inputs sP eP covS covE le_obs (208 B) + index (4 B), per
     //           matched point P + pl_obs (40 B) + index (4 B); per sequence the two Tfw (256 B),
     //           DT_inv and invCov_sum out (128 + 168 B)
     //   finish: per matched line its cut inputs + index + ratios (228 B) read, invCovPose (288 B) and
     //           the cut endpoints sP eP spl epl sdisp edisp (96 B) written
     const bool cut = sb->last_cut_mode >= 0;
-    bytes4[0] = cut ? 212 * v[14] + 44 * v[13] + 552 * (int64_t)sb->B : 0;
-    bytes4[1] = v[7];
-    bytes4[2] = cut ? 612 * v[14] : 0;
-    bytes4[3] = v[5];
+    bytes4[0] = cut ? 212 * v[GFPL_STEP_M_L] + 44 * v[GFPL_STEP_M_P] + 552 * (int64_t)sb->B : 0;
+    bytes4[1] = v[GFPL_STEP_B_CUT_SEARCH];
+    bytes4[2] = cut ? 612 * v[GFPL_STEP_M_L] : 0;
+    bytes4[3] = v[GFPL_STEP_B_POSE];
     return GFPL_OK;
 }
 
 int gfpl_last_step_stage_bytes(gfpl_seqbatch* sb, int64_t* bytes7) {
-    if (!sb || !bytes7) return GFPL_E_INVALID;
-    int64_t v[STEP_REC];
-    int e = step_rec_sums(sb, v);
-    if (e) return e;
-    for (int s = 0; s < 7; ++s) bytes7[s] = v[s];
-    return GFPL_OK;
+    return step_rec_sums(sb, GFPL_STEP_B_STEREO_POINTS, 7, bytes7);
 }
 
 int gfpl_last_step_counts(gfpl_seqbatch* sb, int64_t* counts8) {
-    if (!sb || !counts8) return GFPL_E_INVALID;
-    int64_t v[STEP_REC];
-    int e = step_rec_sums(sb, v);
-    if (e) return e;
-    for (int s = 0; s < 8; ++s) counts8[s] = v[8 + s];
-    return GFPL_OK;
+    return step_rec_sums(sb, GFPL_STEP_N_O, 8, counts8);
 }
 
 int gfpl_last_step_track_counts(gfpl_seqbatch* sb, int64_t* counts4) {
-    if (!sb || !counts4) return GFPL_E_INVALID;
-    int64_t v[STEP_REC];
-    int e = step_rec_sums(sb, v);
-    if (e) return e;
-    for (int s = 0; s < 4; ++s) counts4[s] = v[16 + s];
-    return GFPL_OK;
+    return step_rec_sums(sb, GFPL_STEP_CUT_STEPS, 4, counts4);
 }
 
 int gfpl_last_step_cut_proof(gfpl_seqbatch* sb, int64_t* counts4) {
-    if (!sb || !counts4) return GFPL_E_INVALID;
-    int64_t v[STEP_REC];
-    int e = step_rec_sums(sb, v);
-    if (e) return e;
-    // slots [20..23] are written by k_cut_verify only: report them for a step that ran it
-    const bool on = sb->last_cut_mode == 1 || sb->last_cut_mode == 3;
-    for (int s = 0; s < 4; ++s) counts4[s] = on ? v[20 + s] : 0;
-    return GFPL_OK;
+    // the proof slots are written by k_cut_verify only: report them for a step that ran it
+    return step_rec_sums(sb, GFPL_STEP_PROOF_REDONE, 4, counts4,
+                         sb && (sb->last_cut_mode == 1 || sb->last_cut_mode == 3));
 }
 
 int gfpl_debug_cut_records(gfpl_seqbatch* sb, int b, double* out, int n_lines) {
@@ -1343,17 +1329,13 @@ int gfpl_debug_clocks(gfpl_seqbatch* sb, int64_t* out) {
     if (!sb || !out) return GFPL_E_INVALID;
     if (hipSetDevice(sb->ctx->device) != hipSuccess) return GFPL_E_HIP;
     if (hipStreamSynchronize(sb->ctx->stream) != hipSuccess) return GFPL_E_HIP;
-    return hipMemcpy(out, sb->scr.dbg, (size_t)sb->B * 8 * sizeof(int64_t), hipMemcpyDeviceToHost) == hipSuccess
+    return hipMemcpy(out, sb->scr.dbg, (size_t)sb->B * DBG_REC * sizeof(int64_t), hipMemcpyDeviceToHost) == hipSuccess
                ? GFPL_OK : GFPL_E_HIP;
 }
 
 int gfpl_last_step_bytes(gfpl_seqbatch* sb, int64_t* bytes) {
     if (!bytes) return GFPL_E_INVALID;
-    int64_t v[7];
-    int e = gfpl_last_step_stage_bytes(sb, v);
-    if (e) return e;
-    *bytes = v[6];
-    return GFPL_OK;
+    return step_rec_sums(sb, GFPL_STEP_B_TOTAL, 1, bytes);
 }
 
 }  // extern "C"

@@ -929,4 +929,50 @@ GFPL_DEV int block_exclusive_scan(int v, int* lds /* >= BLOCK/64 + 1 ints */, in
     return r;
 }
 
+// ------------------------------------------------------------ phase clock --
+// Diagnostic builds time a kernel's phases into its sequences' debug slots (DevScratch::dbg; what each
+// slot means under each flag: gfpl_records.hpp).  One compile flag per instrumented kernel:
+//   -DGFPL_CUT_CLOCK -DGFPL_CUT_PCLOCK (k_cut_search)  -DGFPL_CUTW_CLOCK -DGFPL_CUTW_TCLOCK (k_cut_search_w)
+//   -DGFPL_VERIFY_CLOCK (k_cut_verify)  -DGFPL_SP_CLOCK (k_stereo_points)  -DGFPL_SL_CLOCK (k_stereo_lines)
+//   -DGFPL_POSE_CLOCK (k_pose)  -DGFPL_PFIN_CLOCK (k_pose_finish)
+// GFPL_DIAG(flag): true in a build with -Dflag (the name then expands to 1), false otherwise.
+#define GFPL_DIAG_(x) (#x[0] == '1')
+#define GFPL_DIAG(flag) GFPL_DIAG_(flag)
+// PhaseClock<ON, N>: N accumulators of shader-clock cycles: tick(i) adds the cycles since the last
+// tick / start() to phase i and counts it (ticks(i): how often phase i ended); store() writes the
+// accumulators [first, first + n) to consecutive slots.  A plain aggregate (reset() before use), so
+// that it can also live in a kernel's LDS state and be ticked by several functions (k_pose).  The OFF
+// form has no members and every call is empty: a product build carries nothing of it.
+template <bool ON, int N>
+struct PhaseClock {
+    GFPL_DEV void reset() {}
+    GFPL_DEV void start() {}
+    GFPL_DEV void tick(int) {}
+    GFPL_DEV int64_t ticks(int) const { return 0; }
+    GFPL_DEV void store(int64_t*, int = 0, int = N) const {}
+};
+template <int N>
+struct PhaseClock<true, N> {
+    uint64_t acc[N], t0;
+    int64_t n[N];
+    GFPL_DEV void reset() {
+        for (int i = 0; i < N; ++i) { acc[i] = 0; n[i] = 0; }
+        t0 = clock64();
+    }
+    GFPL_DEV void start() { t0 = clock64(); }
+    GFPL_DEV void tick(int i) { const uint64_t t = clock64(); acc[i] += t - t0; t0 = t; ++n[i]; }
+    GFPL_DEV int64_t ticks(int i) const { return n[i]; }
+    GFPL_DEV void store(int64_t* slots, int first = 0, int n_ = N) const {
+        for (int i = 0; i < n_; ++i) slots[i] = (int64_t)acc[first + i];
+    }
+};
+// A tick is a statement of its own, as the hand-written clock macros it replaces were: clang's block
+// order, and with it a product kernel's code, depends on the (empty) do-while standing there.
+#define PHASE_TICK(clk, i) do { (clk).tick(i); } while (0)
+#define PHASE_START(clk) do { (clk).start(); } while (0)
+// the other pattern: the wall clock (100 MHz, comparable between workgroups) at a phase boundary into
+// slot k, by the lanes for which `who` holds
+#define DIAG_STAMP(flag, who, slots, k) \
+    do { if (GFPL_DIAG(flag) && (who)) (slots)[k] = (int64_t)wall_clock64(); } while (0)
+
 }  // namespace gfpl

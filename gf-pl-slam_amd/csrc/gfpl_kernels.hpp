@@ -4,8 +4,18 @@
 #include "gfpl_state.hpp"
 
 #include <atomic>
+#include <cstdlib>
 
 namespace gfpl {
+
+// An integer from the environment (decimal, or hex with 0x), `dflt` when the variable is unset: the
+// launchers' batch-size thresholds and debug switches.  Read at every call, so a process may change
+// a variable between launches (the tests do).
+inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    if (!e) return dflt;
+    return (int)strtol(e, nullptr, (e[0] == '0' && (e[1] == 'x' || e[1] == 'X')) ? 16 : 10);
+}
 
 // A kernel's dynamic-LDS ceiling above the 64 KB default, set once per device (the attribute
 // belongs to the device's kernel object; contexts on several devices may share the process).

@@ -10,6 +10,7 @@
 
 #include "../../include/gfpl.h"
 #include "gfpl_device.hpp"
+#include "gfpl_records.hpp"
 
 namespace gfpl {
 
@@ -72,31 +73,14 @@ struct DevTrack {
     int32_t* kf_flag;      // [B] last needNewKF decision
 };
 
-#define STEP_REC 24   // int64 per sequence in DevScratch::bytes: [0..5] stage bytes, [6] total, [7] k_cut_search,
-                      // [8..15] counts N_o N_k M_o S_p' S_l' M_p M_l n_inliers (gfpl_last_step_counts),
-                      // [16] line-cut search steps, [17] of them evaluated exactly (k_cut_search),
-                      // [18] n_inliers after optimize_pose (k_pose_finish), [19] lines whose agreement bound
-                      // was unusable (k_cut_search: R0 <= 0 or a term not finite; their steps are exact),
-                      // proven mode (k_cut_verify): [20] 1 if the recorded search was not proven (the
-                      // eager-proven search redid it), [21] margined steps verified, [22] the reference's
-                      // endpoint variances evaluated, [23] lines with margined steps
-#define CUT_PATH 64   // proven mode: recorded search steps per line (k_cut_search -> k_cut_verify)
-#define CUT_DTL 4     // proven mode: detail-list entries per sequence (a sequence past them is redone eagerly)
-#define CUT_VMAX 14   // proven mode: doubles per line of k_cut_vref's maxima [0..5] and k_cut_ebound's operand bounds (14 floats at [6..13]) (DevScratch::cut_vmax)
-#define CUT_P_STAY 8  //   step byte: no neighbour beat the centre (the line ends), else the move j (0-7)
-#define CUT_P_EXACT 16 //  step byte flag: the step was decided by the reference's arithmetic (exact round)
-#define CUT_KS 22     // proven line cut: ratio keys per side (KParams::cut_keys)
-#define CUT_FAST 56   // doubles of per-line comparison data (k_cut.hip, PD_*): polynomials, flags, error bounds
-#define CUT_REC 80    // doubles of a per-line cut record: comparison data | r = 0 info (21) | pad (640 B)
-
 struct DevScratch {
     double* cut_rec;  // [B*mls_cap*CUT_REC] per matched line: P(t) coefficients of both cut endpoints, v'(t)
                       // coefficients, geometry flag, list index of the next line | lower-triangle r = 0 info
     int32_t* knn;     // [B*6*kcap] initial-frame knn results (idx0, d0, d1, ...)
     double* proj;     // [B*kcap*2] cross-points projections (aliases knn: init never overlaps)
-    int64_t* bytes;   // [B*STEP_REC] algorithmic bytes of the last step per stage | feature counts
+    int64_t* bytes;   // [B*STEP_REC] the step record: algorithmic bytes of the last step per stage | counts
     int32_t* n_subpix; // [B] left keypoints that reached the sub-pixel SAD (M_o)
-    double* cut_sum;   // [B*24] invCov_sum (lower triangle) after the r=0 pass
+    double* cut_sum;   // [B*CUT_SUM_REC] invCov_sum (lower triangle) after the r=0 pass
     double* cut_dtinv; // [B*16] DT_inv of the line cut
     double* cut_vtab;  // [B*mls_cap*2*CUT_KS] proven line cut: the reference's scaled endpoint variance
                        // per matched line, side and ratio key (k_cut_vtab)
@@ -112,13 +96,13 @@ struct DevScratch {
     double* pose_dtini; // [B*16] staging of gfpl_optimize_pose_ini's DT_ini
     int32_t* kf_mask;  // [B] staging of gfpl_curr_frame_is_kf's mask
     double* cross_tinv; // [B*16] inverse of the predicted curr.Tfw (k_predict_pose -> k_cross_points)
-    int64_t* dbg;       // [B*8] diagnostic clocks (only builds with -DGFPL_SP_CLOCK write them)
+    int64_t* dbg;       // [B*DBG_REC] debug slots: who writes which in which build, gfpl_records.hpp
     int32_t* cut_prog;  // [1 << 17] k_cut_search: lines done per (XCC, SE, SH, CU, SIMD, wave slot)
     uint8_t* cut_path;  // [B*mls_cap*CUT_PATH] proven mode: every line's recorded search steps
     int32_t* cut_flag;  // [B] proven mode: 1 = the recorded search was not proven (redo it eagerly)
     int32_t* cut_offl;  // [1 + B*mls_cap] proven mode: count, then the lines (b * mls_cap + m) k_cut_vref left to k_cut_vref_off
     int32_t* cut_dtln;  // [1 + CUT_DTL * B] proven mode: count, then the lines k_cut_verify left to k_cut_verify_detail
-    double* cut_dtl;    // [CUT_DTL * B * 32] their payload: S_full at the line's start (21), the bound terms (9)
+    double* cut_dtl;    // [CUT_DTL * B * CUT_DTL_REC] their payload: S_full at the line's start, the bound terms
     double* cut_vmax;   // [B*mls_cap*CUT_VMAX] proven mode (k_cut_vref -> k_cut_verify): per line, over the ratios
                         // its margined steps compared, max 1 / v' and max r_v / v' per side, the margined
                         // steps, and the ratios whose v' comparison failed
@@ -146,5 +130,11 @@ struct KParams {
     int cut_nkeys;
     int8_t cut_knxt[CUT_KS], cut_kprv[CUT_KS];
 };
+
+// matched line m of sequence b: its index in the per-line scratch records (cut_rec, cut_vtab, cut_vmax,
+// cut_path) and in matched_ls
+// (a macro: as an inline function taking the parameter block it changed k_cut_vtab's, k_cut_vref's and
+// k_cut_search's code)
+#define LINE_SLOT(p, b, m) ((size_t)(b) * (p).mls_cap + (m))
 
 }  // namespace gfpl

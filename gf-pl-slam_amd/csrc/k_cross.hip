@@ -290,7 +290,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_CL_WAVES) k_cross_lines(KParams p)
                 P.epl_obs[2 * qi] = Cc.epl[2 * qt]; P.epl_obs[2 * qi + 1] = Cc.epl[2 * qt + 1];
                 for (int k = 0; k < 3; ++k) P.le_obs[3 * qi + k] = Cc.le[3 * qt + k];
                 P.inlier[qi] = 1;
-                p.tr.matched_ls[(size_t)b * p.mls_cap + rank] = i;
+                p.tr.matched_ls[LINE_SLOT(p, b, rank)] = i;
                 Cc.idx[qt] = P.idx[qi];
             }
             off += tot;

@@ -4,21 +4,31 @@
 // (include/linespec.h:43-56).
 //
 // The search is a serial chain over matched lines: each line's greedy search
-// reads invCov_sum after all earlier lines were cut.  Three kernels:
-//  k_cut_prep   (one wave / sequence) r = (0,0) infos of lines and points and
-//               invCov_sum, each entry summed in list order (lines, then points)
-//               by one lane over 64-entry chunks staged in LDS;
-//  k_cut_search (8 sequences per wave, 8 lanes each) the greedy search, one step
-//               of every chain per wave iteration (see the comment at the kernel);
-//  k_cut_finish (parallel) full 6x6 info of the chosen ratio (invCovPose) and
-//               the cut endpoints of every matched line.
-// With cut_with_max_vol = 0 the metric is getMinEigenValue(invCov_sum) (:1671-1678, 1712-1719) and
-// k_cut_search_eig takes k_cut_search's place (every step in the reference's arithmetic).
+// reads invCov_sum after all earlier lines were cut.  The kernels (launch_line_cut, in launch order):
+//  k_cut_prep<W>       every mode: r = (0,0) infos of lines and points and invCov_sum, each entry
+//                      summed in list order (lines, then points) by one lane over 64-entry chunks staged
+//                      in LDS; the per-line records (gfpl_records.hpp).  W = 8 waves per sequence up to
+//                      GFPL_CUT_PREP_W8_MAX_B sequences, else 1
+//  the search, one of
+//   k_cut_search_eig   cut_with_max_vol = 0: the metric is getMinEigenValue(invCov_sum) (:1671-1678,
+//                      1712-1719), every step in the reference's arithmetic; cut_proof is not used
+//   k_cut_search_w     cut_proof 0 / 1 / 3, B <= GFPL_CUT_WAVE_MAX_B: one sequence per wave (records its
+//                      steps when cut_proof != 0)
+//   k_cut_search<false>        cut_proof 0, larger B: 8 sequences per wave, 8 lanes each, one step of
+//                      every chain per wave iteration (see the comment at the kernel)
+//   k_cut_search<false, true>  cut_proof 1 / 3, larger B: the same, recording every step
+//   k_cut_search<true> cut_proof 2: the eager-proven search, after k_cut_bounds (per-line operand error
+//                      bounds) and k_cut_vtab (the reference's endpoint variances at the ratio keys)
+//  cut_proof 1 / 3, after the recorded search: k_cut_vref (+ k_cut_vref_off for the lines it leaves) and
+//                      k_cut_ebound, then k_cut_verify (+ k_cut_verify_detail) prove the recorded
+//                      decisions and finish the proven sequences; k_cut_bounds, k_cut_vtab and
+//                      k_cut_search<true> redo the flagged ones
+//  k_cut_finish        every mode (parallel): full 6x6 info of the chosen ratio (invCovPose) and the cut
+//                      endpoints of every matched line
 // Only the lower triangle is carried through the search: LLT reads nothing
 // else (ledger Q11).
-#include <cstdlib>
-
 #include "gfpl_kernels.hpp"
+#include "gfpl_wave.hpp"
 
 namespace gfpl {
 
@@ -174,16 +184,7 @@ __device__ __forceinline__ void load_line(const DevLines& L, size_t q, LineCutDa
 // are searched with the reference's exact steps).  The fgz2 factors cancel in the
 // determinant lemma, so a neighbour's comparison value needs only P and v'.
 // Per matched line, k_cut_prep stores (CUT_FAST doubles):
-#define PD_PS 0      // start side (sP -> eP, t = r0): P coefficients of t^0, t^1, t^2 [3 x 6]
-#define PD_PE 18     // end side (eP -> sP, t = r1) [3 x 6]
-#define PD_VS 36     // v'_s(t) coefficients of t^0 .. t^4 [5]
-#define PD_VE 41     // v'_e(t) [5]
-#define PD_OK 46     // 1.0: gz^2 > 2 homog_th at both ends, one sign (fgz2 = fx / gz^2 on the segment)
-#define PD_NEXT 47   // list index of the line after this one (k_cut_search's prefetch)
-#define PD_ERR 48    // k_cut_bounds: 14 floats (rounded up) packed in 7 doubles, per side (start, end):
-                     // eP[6] (|P(t) - P*(t)|, ours + the reference's endpoint Jacobian in P units) | ev
-                     // (|v'(t) - v'*(t)|), valid for every t of the range; +inf: no margined steps
-static_assert(CUT_FAST == 56, "per-line comparison data layout");
+// the PD_* offsets of gfpl_records.hpp.
 
 // x^T A y, A symmetric packed (xx xy xz yy yz zz)
 template <typename T>
@@ -267,9 +268,6 @@ __device__ __forceinline__ void cut_poly_data(const double* Dl, const LineCutDat
                     ? 1.0 : 0.0;
 }
 
-// a wave's LDS stores visible to its own later loads (one wave: no barrier needed)
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 // ------------------------------------------------------------------ prep --
 // W waves per sequence (W = 1 from CUT_PREP_W8_MAX_B up; small batches W = 8): the waves compute W
 // 64-entry chunks at once, each in its own LDS buffer, then wave 0's lanes e < 21 add the W chunks'
@@ -290,7 +288,7 @@ __global__ void __launch_bounds__(64 * W) k_cut_prep(KParams p) {
     const size_t lb = (size_t)b * p.kl_cap, pbase = (size_t)b * p.kp_cap;
     const int32_t* mls = p.tr.matched_ls + (size_t)b * p.mls_cap;
     const int32_t* mpt = p.tr.matched_pt + (size_t)b * p.mpt_cap;
-    double* rec_l = p.scr.cut_rec + (size_t)b * p.mls_cap * CUT_REC;
+    double* rec_l = p.scr.cut_rec + LINE_SLOT(p, b, 0) * CUT_REC;
     // DT_inv = curr.Tfw^-1 * prev.Tfw (src/stereoFrameHandler.cpp:1635), every lane
     double Dl[16];
     {
@@ -386,7 +384,7 @@ __global__ void __launch_bounds__(64 * W) k_cut_prep(KParams p) {
         }
         __syncthreads();
     }
-    if (wv == 0 && lane < 21) p.scr.cut_sum[24 * b + lane] = s;
+    if (wv == 0 && lane < 21) p.scr.cut_sum[CUT_SUM_REC * b + lane] = s;
 }
 constexpr size_t cut_prep_lds(int w) { return (size_t)w * 21 * 65 * sizeof(double); }
 
@@ -414,13 +412,12 @@ __device__ __forceinline__ float ceil_f32(double x) {
 // expression tree of cut_endpoint_t<double>, hence its bits) and fgz2 = fx / max(homog, gz^2) of
 // the blended point (poseJac's); P(t) of the comparison polynomials is J / fgz2, so the pair
 // (P, v'_ref) carries the reference's info J J^T / v up to the scaling's rounding
-__device__ __forceinline__ double ref_vprime(const DevCam& cam, double homog, const double* Dl, const DevLines& L,
-                                             size_t q, int side, double c) {
-    const double* P0 = side ? L.eP + 3 * q : L.sP + 3 * q;
-    const double* P1 = side ? L.sP + 3 * q : L.eP + 3 * q;
-    const double* C0 = side ? L.covE + 9 * q : L.covS + 9 * q;
-    const double* C1 = side ? L.covS + 9 * q : L.covE + 9 * q;
-    const double Jl[2] = {L.le_obs[3 * q], L.le_obs[3 * q + 1]};
+// ... of one side given as (P0, C0) blended towards (P1, C1); SD: endpointVar_t's shared-reciprocal
+// divisions (k_cut_vref's evaluations, from the line's data held in registers)
+template <bool SD>
+__device__ __forceinline__ double ref_vprime_at(const DevCam& cam, double homog, const double* Dl, const double* P0,
+                                                const double* P1, const double* C0, const double* C1, const double* Jl,
+                                                double c) {
     double Pt[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) Pt[k] = (1.0 - c) * P0[k] + c * P1[k];
@@ -428,11 +425,21 @@ __device__ __forceinline__ double ref_vprime(const DevCam& cam, double homog, co
     double cov[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) cov[i] = a * C0[i] + qq * C1[i];
-    const double v = endpointVar_t<double>(cam, Dl, Jl, Pt, cov, 0.0);
+    const double v = endpointVar_t<double, SD>(cam, Dl, Jl, Pt, cov, 0.0);
     double cur[3];
     se3_apply(Dl, Pt, cur);
     const double f = cam.fx / ref_max(homog, cur[2] * cur[2]);
     return v / (f * f);
+}
+// ... of side `side` of line q (0: sP towards eP, 1: eP towards sP)
+__device__ __forceinline__ double ref_vprime(const DevCam& cam, double homog, const double* Dl, const DevLines& L,
+                                             size_t q, int side, double c) {
+    const double* P0 = side ? L.eP + 3 * q : L.sP + 3 * q;
+    const double* P1 = side ? L.sP + 3 * q : L.eP + 3 * q;
+    const double* C0 = side ? L.covE + 9 * q : L.covS + 9 * q;
+    const double* C1 = side ? L.covS + 9 * q : L.covE + 9 * q;
+    const double Jl[2] = {L.le_obs[3 * q], L.le_obs[3 * q + 1]};
+    return ref_vprime_at<false>(cam, homog, Dl, P0, P1, C0, C1, Jl, c);
 }
 
 // Proven line cut: per matched line, side and ratio key, the reference's endpoint variance scaled
@@ -449,8 +456,8 @@ __global__ void __launch_bounds__(256) k_cut_vtab(KParams p) {
     for (int idx = threadIdx.x; idx < nls * per; idx += 256) {
         const int m = idx / per, r = idx - m * per;
         const int side = r >= nk ? 1 : 0, slot = r - side * nk;
-        const size_t q = (size_t)b * p.kl_cap + p.tr.matched_ls[(size_t)b * p.mls_cap + m];
-        p.scr.cut_vtab[((size_t)b * p.mls_cap + m) * (2 * CUT_KS) + side * CUT_KS + slot] =
+        const size_t q = (size_t)b * p.kl_cap + p.tr.matched_ls[LINE_SLOT(p, b, m)];
+        p.scr.cut_vtab[LINE_SLOT(p, b, m) * (2 * CUT_KS) + side * CUT_KS + slot] =
             ref_vprime(p.cam, p.cfg.homog_th, Dl, L, q, side, p.cut_keys[slot]);
     }
 }
@@ -590,8 +597,8 @@ __global__ void __launch_bounds__(64) k_cut_bounds(KParams p) {
     const int m = blockIdx.x * 64 + threadIdx.x;
     const int nls = p.tr.n_matched_ls[b];
     if (m >= nls || (p.cfg.cut_proof != 2 && p.scr.cut_flag[b] == 0)) return;
-    const size_t q = (size_t)b * p.kl_cap + p.tr.matched_ls[(size_t)b * p.mls_cap + m];
-    double* rec = p.scr.cut_rec + ((size_t)b * p.mls_cap + m) * CUT_REC;
+    const size_t q = (size_t)b * p.kl_cap + p.tr.matched_ls[LINE_SLOT(p, b, m)];
+    double* rec = p.scr.cut_rec + LINE_SLOT(p, b, m) * CUT_REC;
     double Dl[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) Dl[i] = p.scr.cut_dtinv[16 * b + i];
@@ -654,10 +661,6 @@ __global__ void __launch_bounds__(64) k_cut_bounds(KParams p) {
 #endif
 #define CUT_SL 7         // exact endpoint slot (X): v, J[6]
 #define CUT_EP 43        // per-group exact endpoint block: 6 slots + 1 (odd stride)
-#define CUT_NX (CUT_FAST + 21)   // used part of a line record: comparison data | r = 0 info
-static_assert(CUT_REC * 8 == 640 && CUT_NX + 3 <= CUT_REC, "a record is 5 x 128 B: five 16-B loads per lane");
-// record slots CUT_NX .. CUT_NX + 2: the line's agreement bound as k_cut_search formed it (6 floats,
-// CutCmp::eb; diagnostics, gfpl_debug_cut_records)
 
 // One reference-order cut endpoint (cut_endpoint) of line q: side 0 the start
 // endpoint blended sP -> eP, side 1 the end endpoint eP -> sP, at ratio t.
@@ -764,8 +767,7 @@ __device__ __forceinline__ double cut_ours_info(const double* xs, double is, dou
 // reads (ns .. bnd, doubles 0-31) come first and the struct is 16-B aligned, 336 B (84 dwords)
 // long: the per-step load is 16 ds_read_b128 (4 LDS cycles each, 256 B/clk) instead of
 // ds_read2_b64 pairs (8 cycles each, 128 B/clk), and the 8 groups' rows start in 8 disjoint bank
-// quads (84 g mod 64) of a b128 lane group.  Raw offsets (cl[]): ns 0, ne 5, vs 10, ve 15, cc 20,
-// bnd 29, bs 32, be 35.
+// quads (84 g mod 64) of a b128 lane group.  The line open fills it through a double* (CC_*).
 struct __attribute__((aligned(16))) CutCmp {
     double ns[5], ne[5];     // |W_s(t)|^2, |W_e(t)|^2
     double vs[5], ve[5];     // v'_s, v'_e
@@ -779,6 +781,11 @@ struct __attribute__((aligned(16))) CutCmp {
     float eb[6];             // R0, A1, A2, B1, B2, EV
 };
 static_assert(sizeof(CutCmp) == 336, "CutCmp: 84 dwords (bank spread of the 8 groups' rows)");
+enum { CC_NS = 0, CC_NE = 5, CC_VS = 10, CC_VE = 15, CC_CC = 20, CC_BND = 29, CC_BS = 32, CC_BE = 35, CC_END = 38 };
+static_assert(offsetof(CutCmp, ns) == 8 * CC_NS && offsetof(CutCmp, ne) == 8 * CC_NE && offsetof(CutCmp, vs) == 8 * CC_VS &&
+              offsetof(CutCmp, ve) == 8 * CC_VE && offsetof(CutCmp, cc) == 8 * CC_CC && offsetof(CutCmp, bnd) == 8 * CC_BND &&
+              offsetof(CutCmp, bs) == 8 * CC_BS && offsetof(CutCmp, be) == 8 * CC_BE && offsetof(CutCmp, eb) == 8 * CC_END,
+              "CutCmp's fields as double offsets");
 // The step's operands (CutCmp without bs / be), read from LDS each step.
 struct CutReg {
     double ns[5], ne[5], vs[5], ve[5], cc[9], bnd[3];
@@ -866,34 +873,12 @@ __device__ __attribute__((noinline)) double cut_exact_step(const double* sj, con
 }
 
 
-// Group-of-8 exchange on the DPP crossbar (no LDS): xor 1, xor 2 (quad_perm) and
-// the half-row mirror (lane i <-> 7 - i) pair every lane of a group in 3 steps.
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v) {
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false);
-}
-#define DPP_XOR1 0xB1
-#define DPP_XOR2 0x4E
-#define DPP_HALF_MIRROR 0x141
-
 // The reference's j-loop "if (m > metric_init)" over the group's 8 lanes: the
 // largest value, ties to the lowest j, NaN / invalid never chosen; -1 unless it
 // beats the centre metric mc.  (v, j) ends up identical in all 8 lanes.
 // The group's max by three DPP max steps (exact: max selects an operand), then the lowest lane
 // holding it from the wave's ballot — 9 + 4 instructions against 3 x 14 for a (value, index)
 // reduction with tie-breaks (the first strict max is the lowest j attaining the max)
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov_f64(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ int group_first_max(double v, int valid, int j, double mc, double& top) {
     const double x = (valid && v == v) ? v : -__builtin_inf();
     double mx = fmax(x, dpp_mov_f64<DPP_XOR1>(x));
@@ -1075,7 +1060,7 @@ __device__ __attribute__((noinline)) void cut_bound_row(int j, double T, const d
 __device__ __attribute__((noinline)) void cut_bound_line(double T, double tau, const double* cl, const double* fs,
                                                          const double* wg, float* eb) {
     const float* ef = reinterpret_cast<const float*>(fs + PD_ERR);
-    const double Bs = h2(cl[32], cl[33], cl[34], T), Be = h2(cl[35], cl[36], cl[37], T);
+    const double Bs = h2(cl[CC_BS], cl[CC_BS + 1], cl[CC_BS + 2], T), Be = h2(cl[CC_BE], cl[CC_BE + 1], cl[CC_BE + 2], T);
     double sum[8];
     for (int q = 0; q < 8; ++q) {
         double a = wg[6 * q];
@@ -1171,16 +1156,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
     __shared__ double vtab[PROOF ? CUT_G : 1][PROOF ? 2 * CUT_KS : 1];
     __shared__ int cnxt[PROOF ? CUT_KS : 1], cprv[PROOF ? CUT_KS : 1];
     const int lane = threadIdx.x;
-#ifdef GFPL_CUT_CLOCK
-    const uint64_t t_beg = wall_clock64();   // (diagnostic build: the wave's duration in record slot 19)
-#endif
+    constexpr bool CLOCK = GFPL_DIAG(GFPL_CUT_CLOCK);   // (diagnostic build: the wave's start / end and hardware ids)
+    const uint64_t t_beg = CLOCK ? wall_clock64() : 0;
     const int g = lane >> 3, j = lane & 7;
     const int b = blockIdx.x * CUT_G + g;
     if (!PROOF && p.cfg.cut_proof == 0 && j == 0 && b < p.B) {
         // the wave's HW_ID / XCC_ID in the debug slots 6 / 7 of its sequences (measured mode; read by
         // tests/test_gpu_parity.py::test_cut_progress_partner_slots: the progress exchange's slot ^ 1)
-        p.scr.dbg[8 * (size_t)b + 6] = (int64_t)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
-        p.scr.dbg[8 * (size_t)b + 7] = (int64_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));
+        dbg_row(p.scr.dbg, b)[DBG_CUT_HW_ID] = (int64_t)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
+        dbg_row(p.scr.dbg, b)[DBG_CUT_XCC_ID] = (int64_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));
     }
     // proven mode (cut_proof 1 / 3): the eager-proven search runs only for the sequences whose
     // recorded search k_cut_verify did not prove (cut_flag); cut_proof 2 runs it for all of them
@@ -1189,7 +1173,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
     // proven mode, first pass (the measured search): every step's decision is recorded for
     // k_cut_verify — one byte per step and line, CUT_PATH per line
     constexpr bool rec = !PROOF && REC;
-    uint8_t* const path = p.scr.cut_path + (size_t)(live ? b : 0) * p.mls_cap * CUT_PATH;
+    uint8_t* const path = p.scr.cut_path + LINE_SLOT(p, live ? b : 0, 0) * CUT_PATH;
     int lstep = 0;       // steps taken on the current line
     // REC: the current line's recorded steps, per group (stored to HBM when the line finishes)
     __shared__ __attribute__((aligned(8))) uint8_t pth[REC ? CUT_G : 1][REC ? CUT_PATH : 8];
@@ -1200,7 +1184,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
     DevLines& L = p.prev.ls;
     const size_t lb = (size_t)(live ? b : 0) * p.kl_cap;
     const int32_t* mls = p.tr.matched_ls + (size_t)(live ? b : 0) * p.mls_cap;
-    const double* rec_l = p.scr.cut_rec + (size_t)(live ? b : 0) * p.mls_cap * CUT_REC;
+    const double* rec_l = p.scr.cut_rec + LINE_SLOT(p, live ? b : 0, 0) * CUT_REC;
     const double* Dl = p.scr.cut_dtinv + 16 * (size_t)(live ? b : 0);   // DT_inv (exact steps only)
     const double st = p.cfg.cut_step;
     const double rlo = p.cfg.cut_rng[0], rhi = p.cfg.cut_rng[1];
@@ -1237,7 +1221,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
     // comparison polynomials.  Margins need the factor healthy and PD_OK.
     auto open_line = [&]() {
         if (PROOF) {   // the line's v'_ref at every key, both sides (k_cut_vtab), and r = (0, 0)'s slots
-            const double* vt = p.scr.cut_vtab + ((size_t)(live ? b : 0) * p.mls_cap + m) * (2 * CUT_KS);
+            const double* vt = p.scr.cut_vtab + LINE_SLOT(p, live ? b : 0, m) * (2 * CUT_KS);
             for (int idx = j; idx < 2 * CUT_KS; idx += 8) vtab[g][idx] = vt[idx];
             i0 = 0;
             i1 = 0;
@@ -1296,7 +1280,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
         double* cl = reinterpret_cast<double*>(&cmpl[g]);
         if (j < 2) {
             const int a = 3 * j, b2 = a + 1, c2 = a + 2;
-            double* o = cl + 5 * j;   // ns | ne
+            double* o = cl + CC_NS + 5 * j;   // ns | ne
             o[0] = gm[tri(a, a)];
             o[1] = 2.0 * gm[tri(b2, a)];
             o[2] = __builtin_fma(2.0, gm[tri(c2, a)], gm[tri(b2, b2)]);
@@ -1304,15 +1288,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
             o[4] = gm[tri(c2, c2)];
         } else if (j < 4) {
 #pragma unroll
-            for (int i = 0; i < 5; ++i) cl[10 + 5 * (j - 2) + i] = fst[g][PD_VS + 5 * (j - 2) + i];
+            for (int i = 0; i < 5; ++i) cl[CC_VS + 5 * (j - 2) + i] = fst[g][PD_VS + 5 * (j - 2) + i];
         } else if (j < 7) {
             const int i = j - 4;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) cl[20 + 3 * i + k] = gm[tri(3 + k, i)];
+            for (int k = 0; k < 3; ++k) cl[CC_CC + 3 * i + k] = gm[tri(3 + k, i)];
             // |W| with a 1% allowance for the approximate square root (bounds only)
             const double gs = fmax(gm[tri(i, i)], 0.0), ge = fmax(gm[tri(3 + i, 3 + i)], 0.0);
-            cl[32 + i] = gs > 0.0 ? 1.01 * gs * __builtin_amdgcn_rsq(gs) : 0.0;
-            cl[35 + i] = ge > 0.0 ? 1.01 * ge * __builtin_amdgcn_rsq(ge) : 0.0;
+            cl[CC_BS + i] = gs > 0.0 ? 1.01 * gs * __builtin_amdgcn_rsq(gs) : 0.0;
+            cl[CC_BE + i] = ge > 0.0 ? 1.01 * ge * __builtin_amdgcn_rsq(ge) : 0.0;
         }
         wave_lds_sync();
         // the line's bound terms at T (lane 7; see cut_dval), and lanes 0-5 the per-row terms of
@@ -1325,12 +1309,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
         // (CutCmp::eb): per-row terms by lanes 0-5, combined by lane 7
         const double T = fmax(fabs(rlo), fabs(rhi));
         if (j == 7) {
-            const double Bs = h2(cl[32], cl[33], cl[34], T), Be = h2(cl[35], cl[36], cl[37], T);
-            const double VsA = h4abs(cl + 10, T), VeA = h4abs(cl + 15, T);
+            const double Bs = h2(cl[CC_BS], cl[CC_BS + 1], cl[CC_BS + 2], T);
+            const double Be = h2(cl[CC_BE], cl[CC_BE + 1], cl[CC_BE + 2], T);
+            const double VsA = h4abs(cl + CC_VS, T), VeA = h4abs(cl + CC_VE, T);
             const double Bs2 = Bs * Bs, Be2 = Be * Be;
-            cl[29] = __builtin_fma(Bs2 + VsA, Be2 + VeA, Bs2 * Be2);
-            cl[30] = VsA;
-            cl[31] = VeA;
+            cl[CC_BND] = __builtin_fma(Bs2 + VsA, Be2 + VeA, Bs2 * Be2);
+            cl[CC_BND + 1] = VsA;
+            cl[CC_BND + 2] = VeA;
         } else if (PROOF && j < 6) {
             cut_bound_row(j, T, fst[g], sumA[g], tmp[g], wg);
         }
@@ -1346,8 +1331,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
             if (j < 6 && live) reinterpret_cast<float*>(const_cast<double*>(rec_l) + (size_t)m * CUT_REC + CUT_NX)[j] = e6[j];
         }
         // the centre of the first step: d at (0, 0)
-        const double vs0 = PROOF ? vtab[g][0] : cl[10], ve0 = PROOF ? vtab[g][CUT_KS] : cl[15];
-        dc = cut_dcore_p1<PROOF>(cl[0], vs0, cl[5], ve0, cl[20], cl[29], cl[30], cl[31], cmpl[g].eb, tq, c_ok);
+        const double vs0 = PROOF ? vtab[g][0] : cl[CC_VS], ve0 = PROOF ? vtab[g][CUT_KS] : cl[CC_VE];
+        dc = cut_dcore_p1<PROOF>(cl[CC_NS], vs0, cl[CC_NE], ve0, cl[CC_CC], cl[CC_BND], cl[CC_BND + 1], cl[CC_BND + 2],
+                                 cmpl[g].eb, tq, c_ok);
     };
     // Next-line prefetch: right after a line opens the group's lanes copy the next line's
     // record (640 B) from HBM straight into LDS (global_load_lds, no registers); it is
@@ -1373,7 +1359,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
         for (int e = j; e < CUT_FAST; e += 8) fst[g][e] = rec_l[e];
 #pragma unroll
         for (int e = j; e < 21; e += 8) {
-            const double s0 = p.scr.cut_sum[24 * b + e];
+            const double s0 = p.scr.cut_sum[CUT_SUM_REC * b + e];
             sumA[g][e] = s0 - rec_l[CUT_FAST + e];
             sumE[g][e] = s0;
         }
@@ -1393,21 +1379,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
     __shared__ int pslot[1];
     if (!PROOF && lane == 0) pslot[0] = 0;
     __builtin_amdgcn_s_setprio(2);
-#ifdef GFPL_CUT_PCLOCK   // (diagnostic build: shader-clock cycles per phase of the wave in scr.dbg 0-3:
-                         //  step evaluation + decision, exact rounds, bookkeeping, transitions)
-    uint64_t pk[4] = {0, 0, 0, 0};
-    uint64_t pk0 = clock64();
-    int n_it = 0, n_tr = 0;   // loop iterations, transitions (scr.dbg 7: n_it << 32 | n_tr)
-    uint64_t tk[3] = {0, 0, 0}, tk0 = 0;   // transition phases (scr.dbg 4-6): finished line's info + next
-                                           // line's record and S, open_line + prefetch, progress exchange
-#define PCK(i) do { const uint64_t t_ = clock64(); pk[i] += t_ - pk0; pk0 = t_; } while (0)
-#define TCK0() do { tk0 = clock64(); } while (0)
-#define TCK(i) do { const uint64_t t_ = clock64(); tk[i] += t_ - tk0; tk0 = t_; } while (0)
-#else
-#define PCK(i) do { } while (0)
-#define TCK0() do { } while (0)
-#define TCK(i) do { } while (0)
-#endif
+    // (-DGFPL_CUT_PCLOCK: the wave's cycles per phase and per transition part, its iterations / transitions: DbgCutPhase)
+    constexpr bool PCLOCK = GFPL_DIAG(GFPL_CUT_PCLOCK);
+    PhaseClock<PCLOCK, 4> pk;      // step evaluation + decision, exact rounds, bookkeeping (once an iteration), transitions
+    PhaseClock<PCLOCK, 3> tk;      // a transition's parts (each once a transition)
+    pk.reset();
+    tk.reset();
     while (__any(m < nls)) {   // wave-uniform loop; groups that are done idle
         const bool act = m < nls && !pend;
         // ---- lane j: d of neighbour j; the group decision and its margins
@@ -1447,7 +1424,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
         n_exact += exact ? 1 : 0;
         double dnext = top;   // d of the next centre (the chosen neighbour, same bits)
         int cnext = 1;
-        PCK(0);
+        PHASE_TICK(pk, 0);
         if (__any(exact)) {
             // ---- X: the reference's evaluation of this step for the groups that need it
             const CutX xr = cut_exact_round(exact, valid, first, m, m_sync, r0, r1, q_cur, lb, best, mls, rec_l, L.sP, L.eP,
@@ -1461,7 +1438,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
             const int sb = __shfl(bok, src);
             if (exact) { dnext = sd; cnext = sb; }
         }
-        PCK(1);
+        PHASE_TICK(pk, 1);
         int finalize = 0;
         if (rec && act) {   // move j | CUT_P_STAY (no better neighbour) | CUT_P_EXACT, into the group's LDS row
             if (j == 0 && lstep < CUT_PATH)
@@ -1511,16 +1488,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
         // CUT_BATCH groups of the wave wait, one has waited CUT_WAIT iterations, or no
         // group has steps left; one transition then serves all of them, so the wave
         // pays its serial chain (factor, solves, LDS exchanges) fewer times.
-        PCK(2);
+        PHASE_TICK(pk, 2);
         const int npend = __popcll(__ballot(pend)) >> 3;
-#ifdef GFPL_CUT_PCLOCK
-        ++n_it;
-#endif
         if (npend > 0 && (npend >= CUT_BATCH || __any(pend && wait >= CUT_WAIT) || __ballot(m < nls && !pend) == 0)) {
-#ifdef GFPL_CUT_PCLOCK
-            ++n_tr;
-#endif
-            TCK0();
+            PHASE_START(tk);
             double info[3];
             if (pend) {
                 // approximate invCov_sum += info of the chosen ratio (the exact one is
@@ -1606,13 +1577,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
                 }
             }
             wave_lds_sync();
-            TCK(0);
+            PHASE_TICK(tk, 0);
             if (pend) {   // group-uniform; open_line exchanges through LDS only
                 open_line();
                 if (m + 1 < nls) pf_issue(m + 1);
                 pend = 0;
             }
-            TCK(1);
+            PHASE_TICK(tk, 1);
             {
                 // (measured mode: the word the previous transition's DMA landed, after this
                 // transition's vmcnt(0))
@@ -1629,35 +1600,31 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
                                  : "memory", "m0");
                 }
             }
-            TCK(2);
+            PHASE_TICK(tk, 2);
         } else if (pend) {
             ++wait;
         }
-        PCK(3);
+        PHASE_TICK(pk, 3);
     }
-#ifdef GFPL_CUT_PCLOCK
-    if (live && j == 0)
-        for (int i = 0; i < 4; ++i) p.scr.dbg[8 * (size_t)b + i] = (int64_t)pk[i];
-    if (live && j == 0) {
-        for (int i = 0; i < 3; ++i) p.scr.dbg[8 * (size_t)b + 4 + i] = (int64_t)tk[i];
-        p.scr.dbg[8 * (size_t)b + 7] = ((int64_t)n_it << 32) | n_tr;
+    if (PCLOCK && live && j == 0) {
+        int64_t* d = dbg_row(p.scr.dbg, b);
+        pk.store(d + DBG_CPK_PHASES);
+        tk.store(d + DBG_CPK_TRANS);
+        d[DBG_CPK_COUNTS] = (pk.ticks(2) << 32) | tk.ticks(2);   // iterations, transitions
     }
-#endif
-#undef PCK
-#undef TCK0
-#undef TCK
     if (live && j == 0) {
-        p.scr.bytes[(size_t)STEP_REC * b + 16] = n_steps;
-        p.scr.bytes[(size_t)STEP_REC * b + 17] = n_exact;
-        p.scr.bytes[(size_t)STEP_REC * b + 19] = n_unb;
-#ifdef GFPL_CUT_CLOCK
-        const uint64_t t_end = wall_clock64();
-        p.scr.bytes[(size_t)STEP_REC * b + 19] = (int64_t)(t_end - t_beg);
-        p.scr.dbg[8 * (size_t)b + 0] = (int64_t)t_beg;
-        p.scr.dbg[8 * (size_t)b + 1] = (int64_t)t_end;
-        p.scr.dbg[8 * (size_t)b + 2] = (int64_t)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));   // HW_ID
-        p.scr.dbg[8 * (size_t)b + 3] = (int64_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));  // XCC_ID
-#endif
+        step_rec(p.scr.bytes, b)[GFPL_STEP_CUT_STEPS] = n_steps;
+        step_rec(p.scr.bytes, b)[GFPL_STEP_CUT_EXACT] = n_exact;
+        step_rec(p.scr.bytes, b)[GFPL_STEP_CUT_UNBOUNDED] = n_unb;
+        if (CLOCK) {
+            const uint64_t t_end = wall_clock64();
+            int64_t* d = dbg_row(p.scr.dbg, b);
+            step_rec(p.scr.bytes, b)[STEP_CUT_CLOCK_DURATION] = (int64_t)(t_end - t_beg);
+            d[DBG_CCK_BEGIN] = (int64_t)t_beg;
+            d[DBG_CCK_END] = (int64_t)t_end;
+            d[DBG_CCK_HW_ID] = (int64_t)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));
+            d[DBG_CCK_XCC_ID] = (int64_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));
+        }
     }
 }
 
@@ -1678,14 +1645,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GFPL_CU
 #ifndef CUT_WAVE_MAX_B
 #define CUT_WAVE_MAX_B 2048
 #endif
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ int nb_da(int j, int side) {   // neighbour j's offset on a side (nb_step's sign)
-    return nb_off(j, side);
-}
 
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) k_cut_search_w(KParams p) {
     __shared__ double sumA[25];                 // approximate S of the current line
@@ -1707,25 +1666,21 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     DevLines& L = p.prev.ls;
     const size_t lb = (size_t)b * p.kl_cap;
     const int32_t* mls = p.tr.matched_ls + (size_t)b * p.mls_cap;
-    const double* rec_l = p.scr.cut_rec + (size_t)b * p.mls_cap * CUT_REC;
+    const double* rec_l = p.scr.cut_rec + LINE_SLOT(p, b, 0) * CUT_REC;
     const double* Dl = p.scr.cut_dtinv + 16 * (size_t)b;
     const double st = p.cfg.cut_step;
     const double rlo = p.cfg.cut_rng[0], rhi = p.cfg.cut_rng[1];
     const bool rec = p.cfg.cut_proof != 0;
-    uint8_t* const path = p.scr.cut_path + (size_t)b * p.mls_cap * CUT_PATH;
+    uint8_t* const path = p.scr.cut_path + LINE_SLOT(p, b, 0) * CUT_PATH;
     constexpr unsigned long long TRI_ROW = tri_pack(1), TRI_COL = tri_pack(0);
     int m = 0, m_sync = 0, first = 1, line_ok = 0, c_ok = 0, lstep = 0;
     double r0 = 0.0, r1 = 0.0, dc = 0.0;
     size_t q_cur = 0;
     int n_steps = 0, n_exact = 0;
     // A line opens (fst and sumA hold its data): the k_cut_search<false> open, one lane per role
-#ifdef GFPL_CUTW_TCLOCK   // (diagnostic build: line-transition phases in scr.dbg 0-7)
-    uint64_t tk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t tk0 = clock64();
-#define TCK(i) do { const uint64_t t_ = clock64(); tk[i] += t_ - tk0; tk0 = t_; } while (0)
-#else
-#define TCK(i) do { } while (0)
-#endif
+    constexpr bool TCLOCK = GFPL_DIAG(GFPL_CUTW_TCLOCK);   // (diagnostic build: cycles of a line transition's parts)
+    PhaseClock<TCLOCK, 7> tk;
+    tk.reset();
     auto open_line = [&]() {
         double o[28];
         {
@@ -1734,7 +1689,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             for (int e = 0; e < 21; ++e) S[e] = sumA[e];
             chol_s(S, o);
         }
-        TCK(2);
+        PHASE_TICK(tk, 2);
         line_ok = (o[27] != 0.0) && (fst[PD_OK] != 0.0);
         if (lane < 6) {
             double w[6];
@@ -1749,7 +1704,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             for (int i = 0; i < 6; ++i) wgs[6 * lane + i] = w[i];
         }
         wave_lds_sync();
-        TCK(3);
+        PHASE_TICK(tk, 3);
         if (lane < 21) {
             const int ra = (int)((TRI_ROW >> (3 * lane)) & 7), cb = (int)((TRI_COL >> (3 * lane)) & 7);
             double s = wgs[6 * ra] * wgs[6 * cb];
@@ -1758,56 +1713,58 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             wgs[36 + lane] = s;
         }
         wave_lds_sync();
-        TCK(4);
+        PHASE_TICK(tk, 4);
         // the line's comparison data (cmpl), formed by every lane in registers (no per-role branches and
         // LDS round trips), stored by lane 0 for the rounds' cut_reg_load
         const double* gm = wgs + 36;
         double* cl = reinterpret_cast<double*>(&cmpl);
-        double G[21], cv[38];
+        double G[21], cv[CC_END];
 #pragma unroll
         for (int e = 0; e < 21; ++e) G[e] = gm[e];
 #pragma unroll
-        for (int i = 0; i < 10; ++i) cv[10 + i] = fst[PD_VS + i];
+        for (int i = 0; i < 10; ++i) cv[CC_VS + i] = fst[PD_VS + i];
 #pragma unroll
         for (int sd = 0; sd < 2; ++sd) {
             const int a0 = 3 * sd, b2 = a0 + 1, c2 = a0 + 2;
-            cv[5 * sd + 0] = G[tri(a0, a0)];
-            cv[5 * sd + 1] = 2.0 * G[tri(b2, a0)];
-            cv[5 * sd + 2] = __builtin_fma(2.0, G[tri(c2, a0)], G[tri(b2, b2)]);
-            cv[5 * sd + 3] = 2.0 * G[tri(c2, b2)];
-            cv[5 * sd + 4] = G[tri(c2, c2)];
+            cv[CC_NS + 5 * sd + 0] = G[tri(a0, a0)];
+            cv[CC_NS + 5 * sd + 1] = 2.0 * G[tri(b2, a0)];
+            cv[CC_NS + 5 * sd + 2] = __builtin_fma(2.0, G[tri(c2, a0)], G[tri(b2, b2)]);
+            cv[CC_NS + 5 * sd + 3] = 2.0 * G[tri(c2, b2)];
+            cv[CC_NS + 5 * sd + 4] = G[tri(c2, c2)];
         }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) cv[20 + 3 * i + k] = G[tri(3 + k, i)];
+            for (int k = 0; k < 3; ++k) cv[CC_CC + 3 * i + k] = G[tri(3 + k, i)];
             const double gs = fmax(G[tri(i, i)], 0.0), ge = fmax(G[tri(3 + i, 3 + i)], 0.0);
-            cv[32 + i] = gs > 0.0 ? 1.01 * gs * __builtin_amdgcn_rsq(gs) : 0.0;
-            cv[35 + i] = ge > 0.0 ? 1.01 * ge * __builtin_amdgcn_rsq(ge) : 0.0;
+            cv[CC_BS + i] = gs > 0.0 ? 1.01 * gs * __builtin_amdgcn_rsq(gs) : 0.0;
+            cv[CC_BE + i] = ge > 0.0 ? 1.01 * ge * __builtin_amdgcn_rsq(ge) : 0.0;
         }
         {
             const double T = fmax(fabs(rlo), fabs(rhi));
-            const double Bs = h2(cv[32], cv[33], cv[34], T), Be = h2(cv[35], cv[36], cv[37], T);
-            const double VsA = h4abs(cv + 10, T), VeA = h4abs(cv + 15, T);
+            const double Bs = h2(cv[CC_BS], cv[CC_BS + 1], cv[CC_BS + 2], T);
+            const double Be = h2(cv[CC_BE], cv[CC_BE + 1], cv[CC_BE + 2], T);
+            const double VsA = h4abs(cv + CC_VS, T), VeA = h4abs(cv + CC_VE, T);
             const double Bs2 = Bs * Bs, Be2 = Be * Be;
-            cv[29] = __builtin_fma(Bs2 + VsA, Be2 + VeA, Bs2 * Be2);
-            cv[30] = VsA;
-            cv[31] = VeA;
+            cv[CC_BND] = __builtin_fma(Bs2 + VsA, Be2 + VeA, Bs2 * Be2);
+            cv[CC_BND + 1] = VsA;
+            cv[CC_BND + 2] = VeA;
         }
         if (lane == 0) {
 #pragma unroll
-            for (int i = 0; i < 38; ++i) cl[i] = cv[i];
+            for (int i = 0; i < CC_END; ++i) cl[i] = cv[i];
         }
         wave_lds_sync();
-        TCK(5);
-        dc = cut_dcore_p1<false>(cv[0], cv[10], cv[5], cv[15], cv[20], cv[29], cv[30], cv[31], cmpl.eb, tq, c_ok);
-        TCK(6);
+        PHASE_TICK(tk, 5);
+        dc = cut_dcore_p1<false>(cv[CC_NS], cv[CC_VS], cv[CC_NE], cv[CC_VE], cv[CC_CC], cv[CC_BND], cv[CC_BND + 1],
+                                 cv[CC_BND + 2], cmpl.eb, tq, c_ok);
+        PHASE_TICK(tk, 6);
     };
     if (nls > 0) {
         q_cur = lb + mls[0];
         for (int e = lane; e < CUT_FAST; e += 64) fst[e] = rec_l[e];
         if (lane < 21) {
-            const double s0 = p.scr.cut_sum[24 * b + lane];
+            const double s0 = p.scr.cut_sum[CUT_SUM_REC * b + lane];
             sumA[lane] = s0 - rec_l[CUT_FAST + lane];
             sumE[lane] = s0;
         }
@@ -1829,13 +1786,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
     };
     prefetch(1);
-#ifdef GFPL_CUTW_CLOCK   // (diagnostic build: shader-clock cycles per phase and counts in scr.dbg)
-    uint64_t ck_eval = 0, ck_dec = 0, ck_walk = 0, ck_trans = 0, ck_exact = 0, n_rounds = 0, n_trans = 0;
-    uint64_t ck0 = clock64();
-#define CUTW_CK(acc) do { const uint64_t ck1 = clock64(); acc += ck1 - ck0; ck0 = ck1; } while (0)
-#else
-#define CUTW_CK(acc) do { } while (0)
-#endif
+    // (-DGFPL_CUTW_CLOCK: the wave's cycles per phase and its rounds / transitions: DbgCutW)
+    constexpr bool WCLOCK = GFPL_DIAG(GFPL_CUTW_CLOCK);
+    enum { CK_EVAL, CK_DEC, CK_WALK, CK_EXACT, CK_TRANS };
+    PhaseClock<WCLOCK, 5> ck;
+    ck.reset();
     while (m < nls) {   // (wave-uniform)
         // ---- the 8 x 8 grid of ratios at offsets -1 .. 6 from the centre, as the moves accumulate
         //      them
@@ -1896,7 +1851,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 dgf[slot] = abok | (valid << 1) | ((valid && !(da == da)) ? 4 : 0);
             }
         }
-        CUTW_CK(ck_eval);
+        PHASE_TICK(ck, CK_EVAL);
         // ---- every grid position's decision at once: lane (a, c), 1 <= a, c <= 6, gathers its 8
         //      neighbours' values (bpermute) and takes k_cut_search's group decision and margin tests
         //      (group_first_max, f1-f5) with its own value as the centre: a move j, CUT_P_STAY, or
@@ -1920,7 +1875,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             if (inc0 | inc1) {   // (wave-uniform) some lower neighbours are alt values
 #pragma unroll
                 for (int jn = 0; jn < 8; ++jn) {
-                    const int da = nb_da(jn, 0), dc = nb_da(jn, 1);
+                    const int da = nb_off(jn, 0), dc = nb_off(jn, 1);
                     const bool xa = ia && da < 0, xc = ic && dc < 0;
                     const int l = (xa && xc) ? 82 + 16 : (xa ? 82 + c + dc : (xc ? 90 + a + da : 9 + lane + 8 * da + dc));
                     vjn[jn] = dgx[l];
@@ -1929,7 +1884,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             } else {   // every neighbour on the grid: constant offsets from the lane's slot
 #pragma unroll
                 for (int jn = 0; jn < 8; ++jn) {
-                    const int l = 9 + lane + 8 * nb_da(jn, 0) + nb_da(jn, 1);
+                    const int l = 9 + lane + 8 * nb_off(jn, 0) + nb_off(jn, 1);
                     vjn[jn] = dgx[l];
                     fl[jn] = dgf[l];
                 }
@@ -1965,16 +1920,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const bool ok = fail == 0;
             // a move below a served index leaves the grid, and the exact round reads the grid's neighbours:
             // both stop the walk (the next round, centred there, has them on its grid)
-            const bool off = has && ((ia && nb_da(best, 0) < 0) || (ic && nb_da(best, 1) < 0));
+            const bool off = has && ((ia && nb_off(best, 0) < 0) || (ic && nb_off(best, 1) < 0));
             dec = !cons ? WAVE_STOP : (!ok ? ((ia || ic) ? WAVE_STOP : WAVE_EXACT) : (off ? WAVE_STOP : (has ? best : CUT_P_STAY)));
             // the walk's word: the decision, whether the move ends the line (r0 + r1 > 1 after it: the moved
             // ratios are the neighbour's grid values, bit for bit, at a consistent position) and the lane moved to
             const int mv = has ? best : 0;
             const double n0 = t0 + nb_step(mv, 0, st), n1 = t1 + nb_step(mv, 1, st);
             const int fin = (has && !(n0 + n1 <= 1.0)) ? 64 : 0;
-            dec |= fin | ((lane + 8 * nb_da(mv, 0) + nb_da(mv, 1)) & 63) << 8;
+            dec |= fin | ((lane + 8 * nb_off(mv, 0) + nb_off(mv, 1)) & 63) << 8;
         }
-        CUTW_CK(ck_dec);
+        PHASE_TICK(ck, CK_DEC);
         // ---- follow the decisions from the centre while they stay inside the grid
         int pos = 9;   // (a, c) = (1, 1): the centre
         int exact = 0, finalize = 0;
@@ -2036,7 +1991,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const int pa = pos >> 3, pc = pos & 7;
 #pragma unroll
             for (int jn = 0; jn < 8; ++jn) {
-                const int l = (pa + nb_da(jn, 0)) * 8 + (pc + nb_da(jn, 1));
+                const int l = (pa + nb_off(jn, 0)) * 8 + (pc + nb_off(jn, 1));
                 vj[jn] = readlane_f64(dj, l);
                 bj[jn] = __builtin_amdgcn_readlane(bok, l);
                 valj[jn] = __builtin_amdgcn_readlane(dj_valid, l);
@@ -2045,10 +2000,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         // the ratios where the walk stopped: that lane's grid values (r + s accumulated, bit for bit)
         r0 = readlane_f64(t0, pos);
         r1 = readlane_f64(t1, pos);
-        CUTW_CK(ck_walk);
-#ifdef GFPL_CUTW_CLOCK
-        ++n_rounds;
-#endif
+        PHASE_TICK(ck, CK_WALK);
         if (exact) {
             // the reference's evaluation of this step (group 0 = lanes 0-7; the flush uses the wave);
             // the neighbours' values were gathered by the step that stopped
@@ -2082,14 +2034,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 if (!(r0 + r1 <= 1.0)) finalize = 1;
             }
         }
-        CUTW_CK(ck_exact);
+        PHASE_TICK(ck, CK_EXACT);
         if (finalize) {
-#ifdef GFPL_CUTW_CLOCK
-            ++n_trans;
-#endif
-#ifdef GFPL_CUTW_TCLOCK
-            tk0 = clock64();
-#endif
+            PHASE_START(tk);
             if (lane == 0) {
                 L.cut[2 * q_cur] = r0;
                 L.cut[2 * q_cur + 1] = r1;
@@ -2119,7 +2066,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 }
             }
             ++m;
-            TCK(0);
+            PHASE_TICK(tk, 0);
             if (m < nls) {
                 wave_lds_sync();
                 if (lane < CUT_FAST) fst[lane] = pf_f0;
@@ -2130,25 +2077,25 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 r0 = 0.0;
                 r1 = 0.0;
                 wave_lds_sync();
-                TCK(1);
+                PHASE_TICK(tk, 1);
                 open_line();
                 prefetch(m + 1);
             }
         }
-        CUTW_CK(ck_trans);
+        PHASE_TICK(ck, CK_TRANS);
     }
     if (lane == 0) {
-        p.scr.bytes[(size_t)STEP_REC * b + 16] = n_steps;
-        p.scr.bytes[(size_t)STEP_REC * b + 17] = n_exact;
-        p.scr.bytes[(size_t)STEP_REC * b + 19] = 0;
-#ifdef GFPL_CUTW_CLOCK
-        int64_t* d = p.scr.dbg + 8 * (size_t)b;
-        d[0] = ck_eval; d[1] = ck_dec; d[2] = ck_walk; d[3] = ck_exact; d[4] = ck_trans; d[5] = n_rounds; d[6] = n_trans;
-        d[7] = n_steps;
-#endif
-#ifdef GFPL_CUTW_TCLOCK
-        for (int i = 0; i < 7; ++i) p.scr.dbg[8 * (size_t)b + i] = (int64_t)tk[i];
-#endif
+        step_rec(p.scr.bytes, b)[GFPL_STEP_CUT_STEPS] = n_steps;
+        step_rec(p.scr.bytes, b)[GFPL_STEP_CUT_EXACT] = n_exact;
+        step_rec(p.scr.bytes, b)[GFPL_STEP_CUT_UNBOUNDED] = 0;
+        if (WCLOCK) {
+            int64_t* d = dbg_row(p.scr.dbg, b);
+            ck.store(d + DBG_CWK_PHASES);
+            d[DBG_CWK_ROUNDS] = ck.ticks(CK_WALK);   // (the walk ends a round)
+            d[DBG_CWK_TRANS] = m;                    // (a transition per line)
+            d[DBG_CWK_STEPS] = n_steps;
+        }
+        if (TCLOCK) tk.store(dbg_row(p.scr.dbg, b));
     }
 }
 
@@ -2184,7 +2131,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     DevLines& L = p.prev.ls;
     const size_t lb = (size_t)(seq ? b : 0) * p.kl_cap;
     const int32_t* mls = p.tr.matched_ls + (size_t)(seq ? b : 0) * p.mls_cap;
-    const double* rec_l = p.scr.cut_rec + (size_t)(seq ? b : 0) * p.mls_cap * CUT_REC;
+    const double* rec_l = p.scr.cut_rec + LINE_SLOT(p, seq ? b : 0, 0) * CUT_REC;
     const double st = p.cfg.cut_step;
     const double rlo = p.cfg.cut_rng[0], rhi = p.cfg.cut_rng[1];
     const double nb0 = nb_step(j, 0, st), nb1 = nb_step(j, 1, st);
@@ -2228,7 +2175,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
         for (int kk = 0; kk < 3; ++kk) {
             const int e = j + 8 * kk;
-            if (e < 21) se[kk] = p.scr.cut_sum[24 * (size_t)b + e];
+            if (e < 21) se[kk] = p.scr.cut_sum[CUT_SUM_REC * (size_t)b + e];
         }
         open_line();
     }
@@ -2316,11 +2263,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     n_sweeps += __shfl_xor(n_sweeps, 1); n_sweeps += __shfl_xor(n_sweeps, 2); n_sweeps += __shfl_xor(n_sweeps, 4);
     n_eval += __shfl_xor(n_eval, 1); n_eval += __shfl_xor(n_eval, 2); n_eval += __shfl_xor(n_eval, 4);
     if (seq && j == 0) {
-        p.scr.bytes[(size_t)STEP_REC * b + 16] = n_steps;
-        p.scr.bytes[(size_t)STEP_REC * b + 17] = n_steps;
-        p.scr.bytes[(size_t)STEP_REC * b + 19] = 0;
-        p.scr.dbg[8 * (size_t)b + 0] = n_sweeps;
-        p.scr.dbg[8 * (size_t)b + 1] = n_eval;
+        step_rec(p.scr.bytes, b)[GFPL_STEP_CUT_STEPS] = n_steps;
+        step_rec(p.scr.bytes, b)[GFPL_STEP_CUT_EXACT] = n_steps;
+        step_rec(p.scr.bytes, b)[GFPL_STEP_CUT_UNBOUNDED] = 0;
+        dbg_row(p.scr.dbg, b)[DBG_EIG_SWEEPS] = n_sweeps;
+        dbg_row(p.scr.dbg, b)[DBG_EIG_EVALS] = n_eval;
     }
 }
 
@@ -2414,41 +2361,20 @@ __global__ void __launch_bounds__(64, GFPL_FIN_WAVES) k_cut_finish(KParams p) {
 // also k_cut_finish for the proven sequences: invCovPose of every line (written for all; a redone
 // sequence overwrites it) and, once the whole sequence is proven, the cut endpoints.
 // One wave per sequence; lines in chunks of 64, one per lane.
-__device__ __forceinline__ double verify_vref(const KParams& p, const double* Dl, size_t q, int side, double t) {
-    return ref_vprime(p.cam, p.cfg.homog_th, Dl, p.prev.ls, q, side, t);
-}
-
 // Proven mode, first verification pass: one lane per matched line of every sequence (no serial
 // dependence between lines here).  The line's recorded steps are replayed and, at every ratio a
-// margined step compared, the reference's own scaled endpoint variance v'_ref (ref_vprime, from
+// margined step compared, the reference's own scaled endpoint variance v'_ref (ref_vprime_at<true>, from
 // the line's data held in registers) is set against the quartic v'_ours the search used:
 // per side, max 1.01 / min(v'_ours, v'_ref) and max r_v / min(...) with r_v = |v'_ours - v'_ref| / v'_ref.
 // k_cut_verify combines these maxima with the line's S-dependent bound terms.
-__device__ __forceinline__ double vref_regs(const DevCam& cam, double homog, const double* Dl, const double* P0,
-                                            const double* P1, const double* C0, const double* C1, const double* Jl,
-                                            double c) {
-    double Pt[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) Pt[k] = (1.0 - c) * P0[k] + c * P1[k];
-    const double a = (1.0 - c) * (1.0 - c), qq = c * c;
-    double cov[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) cov[i] = a * C0[i] + qq * C1[i];
-    const double v = endpointVar_t<double, true>(cam, Dl, Jl, Pt, cov, 0.0);
-    double cur[3];
-    se3_apply(Dl, Pt, cur);
-    const double f = cam.fx / ref_max(homog, cur[2] * cur[2]);
-    return v / (f * f);
-}
-
 // The line's replay with a small cache of evaluated ratios per side: the fallback of k_cut_vref for a
 // line whose compared ratios leave the key table (a ratio moved back: rare), one lane.
 __device__ __forceinline__ void vref_replay(const KParams& p, int b, int m) {
-    const double* fd = p.scr.cut_rec + ((size_t)b * p.mls_cap + m) * CUT_REC;
-    double* out = p.scr.cut_vmax + ((size_t)b * p.mls_cap + m) * CUT_VMAX;
-    const uint8_t* path = p.scr.cut_path + ((size_t)b * p.mls_cap + m) * CUT_PATH;
+    const double* fd = p.scr.cut_rec + LINE_SLOT(p, b, m) * CUT_REC;
+    double* out = p.scr.cut_vmax + LINE_SLOT(p, b, m) * CUT_VMAX;
+    const uint8_t* path = p.scr.cut_path + LINE_SLOT(p, b, m) * CUT_PATH;
     const DevLines& L = p.prev.ls;
-    const size_t q = (size_t)b * p.kl_cap + p.tr.matched_ls[(size_t)b * p.mls_cap + m];
+    const size_t q = (size_t)b * p.kl_cap + p.tr.matched_ls[LINE_SLOT(p, b, m)];
     const double* Dl = p.scr.cut_dtinv + 16 * (size_t)b;
     const double st = p.cfg.cut_step, rlo = p.cfg.cut_rng[0], rhi = p.cfg.cut_rng[1];
     double sP[3], eP[3], cS[9], cE[9], Jl[2], qs[5], qe[5];
@@ -2488,8 +2414,8 @@ __device__ __forceinline__ void vref_replay(const KParams& p, int b, int m) {
                     hit = hit || h;
                 }
                 if (!hit) {
-                    vr = side ? vref_regs(p.cam, p.cfg.homog_th, Dl, eP, sP, cE, cS, Jl, t)
-                              : vref_regs(p.cam, p.cfg.homog_th, Dl, sP, eP, cS, cE, Jl, t);
+                    vr = side ? ref_vprime_at<true>(p.cam, p.cfg.homog_th, Dl, eP, sP, cE, cS, Jl, t)
+                              : ref_vprime_at<true>(p.cam, p.cfg.homog_th, Dl, sP, eP, cS, cE, Jl, t);
                     ++nev;
 #pragma unroll
                     for (int z = 0; z < 4; ++z) {
@@ -2567,7 +2493,7 @@ __global__ void __launch_bounds__(64) k_cut_vref(KParams p) {
     bool off = nk == 0;
     if (on && !off) {
         // the line's 64 path bytes in one go (16-byte loads), not a memory round trip per step
-        const uint4* pv = reinterpret_cast<const uint4*>(p.scr.cut_path + ((size_t)b * p.mls_cap + m) * CUT_PATH);
+        const uint4* pv = reinterpret_cast<const uint4*>(p.scr.cut_path + LINE_SLOT(p, b, m) * CUT_PATH);
         uint32_t pw[CUT_PATH / 4];
 #pragma unroll
         for (int i = 0; i < CUT_PATH / 16; ++i) {
@@ -2609,7 +2535,7 @@ __global__ void __launch_bounds__(64) k_cut_vref(KParams p) {
                 if (!(r[0] + r[1] <= 1.0)) done = true;
             }
         }
-        const int qi = p.tr.matched_ls[(size_t)b * p.mls_cap + m];
+        const int qi = p.tr.matched_ls[LINE_SLOT(p, b, m)];
         qln[lane] = qi;
         const size_t q = (size_t)b * p.kl_cap + qi;
         // a path that does not end where the search's final ratios are counts as a failure
@@ -2650,7 +2576,7 @@ __global__ void __launch_bounds__(64) k_cut_vref(KParams p) {
             const int ln = it >> 6, side = (it >> 5) & 1, kk = it & 31;
             const int mm = blockIdx.x * 64 + ln;
             const size_t q = (size_t)b * p.kl_cap + qln[ln];
-            const double* fd = p.scr.cut_rec + ((size_t)b * p.mls_cap + mm) * CUT_REC;
+            const double* fd = p.scr.cut_rec + LINE_SLOT(p, b, mm) * CUT_REC;
             double P0[3], P1[3], C0[9], C1[9], Jl[2], qc[5];
             const double* A3 = side ? L.eP : L.sP;
             const double* B3 = side ? L.sP : L.eP;
@@ -2665,7 +2591,7 @@ __global__ void __launch_bounds__(64) k_cut_vref(KParams p) {
 #pragma unroll
             for (int k = 0; k < 5; ++k) qc[k] = fd[(side ? PD_VE : PD_VS) + k];
             const double t = keys[kk];
-            const double vr = vref_regs(p.cam, p.cfg.homog_th, Dl, P0, P1, C0, C1, Jl, t);
+            const double vr = ref_vprime_at<true>(p.cam, p.cfg.homog_th, Dl, P0, P1, C0, C1, Jl, t);
             const double vo = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, qc[4], qc[3]), qc[2]),
                                                              qc[1]), qc[0]);   // (cut_ours_V's expression)
             const double lo = fmin(vr, vo);
@@ -2681,7 +2607,7 @@ __global__ void __launch_bounds__(64) k_cut_vref(KParams p) {
     }
     wave_lds_sync();
     if (!on) return;
-    double* out = p.scr.cut_vmax + ((size_t)b * p.mls_cap + m) * CUT_VMAX;
+    double* out = p.scr.cut_vmax + LINE_SLOT(p, b, m) * CUT_VMAX;
     if (off) {   // (k_cut_vref_off replays the line: appended to its list)
         const int slot = atomicAdd(p.scr.cut_offl, 1);
         p.scr.cut_offl[1 + slot] = b * p.mls_cap + m;
@@ -2710,15 +2636,15 @@ __global__ void __launch_bounds__(64) k_cut_ebound(KParams p) {
     const int b = blockIdx.y;
     const int m = blockIdx.x * 64 + threadIdx.x;
     if (m >= p.tr.n_matched_ls[b]) return;
-    const double* fd = p.scr.cut_rec + ((size_t)b * p.mls_cap + m) * CUT_REC;
+    const double* fd = p.scr.cut_rec + LINE_SLOT(p, b, m) * CUT_REC;
     if (fd[PD_OK] == 0.0) return;
-    const size_t q = (size_t)b * p.kl_cap + p.tr.matched_ls[(size_t)b * p.mls_cap + m];
+    const size_t q = (size_t)b * p.kl_cap + p.tr.matched_ls[LINE_SLOT(p, b, m)];
     double Dl[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) Dl[i] = p.scr.cut_dtinv[16 * b + i];
     float eb[14];
     cut_line_bounds_p(p, q, true, Dl, eb);
-    float* o = reinterpret_cast<float*>(p.scr.cut_vmax + ((size_t)b * p.mls_cap + m) * CUT_VMAX + 6);
+    float* o = reinterpret_cast<float*>(p.scr.cut_vmax + LINE_SLOT(p, b, m) * CUT_VMAX + CUT_VMAX_EB);
 #pragma unroll
     for (int i = 0; i < 14; ++i) o[i] = eb[i];
 }
@@ -2801,7 +2727,7 @@ __device__ __attribute__((noinline)) int verify_line_detail(const KParams& p, co
                         for (int z = 0; z < cn[side]; ++z)
                             if (__double_as_longlong(ct[side][z]) == __double_as_longlong(t)) { vr = cv[side][z]; hit = true; }
                         if (!hit) {
-                            vr = verify_vref(p, Dl, q, side, t);
+                            vr = ref_vprime(p.cam, p.cfg.homog_th, Dl, p.prev.ls, q, side, t);
                             const int z = cn[side] < 4 ? cn[side]++ : (k & 3);
                             ct[side][z] = t;
                             cv[side][z] = vr;
@@ -2965,7 +2891,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     DevLines& L = p.prev.ls;
     const size_t lb = (size_t)b * p.kl_cap;
     const int32_t* mls = p.tr.matched_ls + (size_t)b * p.mls_cap;
-    const double* rec_l = p.scr.cut_rec + (size_t)b * p.mls_cap * CUT_REC;
+    const double* rec_l = p.scr.cut_rec + LINE_SLOT(p, b, 0) * CUT_REC;
     double Dl[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) Dl[i] = p.scr.cut_dtinv[16 * b + i];
@@ -2979,17 +2905,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     // the whole sum before the line's r = 0 info is taken out), lanes 0-20 hold entry lane
     double sA = 0.0, sE = 0.0;
     if (nls > 0 && lane < 21) {
-        const double s0 = p.scr.cut_sum[24 * b + lane];
+        const double s0 = p.scr.cut_sum[CUT_SUM_REC * b + lane];
         sA = s0 - rec_l[CUT_FAST + lane];
         sE = s0;
     }
-#ifdef GFPL_VERIFY_CLOCK   // (diagnostic build: shader-clock cycles per phase in scr.dbg 0-4)
-    uint64_t vk[5] = {0, 0, 0, 0, 0};
-    uint64_t vk0 = clock64();
-#define VK(i) do { const uint64_t vk1 = clock64(); vk[i] += vk1 - vk0; vk0 = vk1; } while (0)
-#else
-#define VK(i) do { } while (0)
-#endif
+    constexpr bool VCLOCK = GFPL_DIAG(GFPL_VERIFY_CLOCK);   // (diagnostic build: cycles of the five per-line phases)
+    PhaseClock<VCLOCK, 5> vk;
+    vk.reset();
     for (int c0 = 0; c0 < nls; c0 += 64) {   // (wave-uniform)
         const int m = c0 + lane;
         const bool on = m < nls;
@@ -3012,7 +2934,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                     for (int k = 0; k <= i; ++k) fr[tri(i, k)][lane] = info[i * 6 + k];
             }
         }
-        VK(0);
+        PHASE_TICK(vk, 0);
         // (2) the search's own info of the line (its transition's expressions, cut_ours_*)
         const bool pdok = fd[PD_OK] != 0.0;
         {
@@ -3035,7 +2957,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             }
         }
         wave_lds_sync();
-        VK(1);
+        PHASE_TICK(vk, 1);
         // (3) the two running sums in list order (lanes 0-20, entry lane): S_ours and the reference's
         //     whole sum at each line's start replace its infos in fo / fr
         const int cnt = min(64, nls - c0);
@@ -3068,25 +2990,25 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             }
         }
         wave_lds_sync();
-        VK(2);
+        PHASE_TICK(vk, 2);
         // (4) the line's bound terms from S_ours, S_ref = sE - i0, and the operand bounds
         double K0 = 0.0, A1 = 0.0, B1 = 0.0, cs = 0.0, ce = 0.0, R0 = -1.0, rts = 0.0, rte = 0.0;
         double epsS_l = 0.0, kt_l = 0.0;
         bool line_ok = false;
         if (on && pdok) {
-            const LineBound lbd = verify_line_bound(p, q, fd, p.scr.cut_vmax + ((size_t)b * p.mls_cap + m) * CUT_VMAX, Dl,
+            const LineBound lbd = verify_line_bound(p, q, fd, p.scr.cut_vmax + LINE_SLOT(p, b, m) * CUT_VMAX, Dl,
                                                     &fo[0][0] + lane, &fr[0][0] + lane);
             K0 = lbd.K0; A1 = lbd.A1; B1 = lbd.B1; cs = lbd.cs; ce = lbd.ce; R0 = lbd.R0; rts = lbd.rts; rte = lbd.rte;
             epsS_l = lbd.epsS; kt_l = lbd.kt; line_ok = lbd.ok != 0;
         }
-        VK(3);
+        PHASE_TICK(vk, 3);
         // (5) the line's margined steps: with k_cut_vref's maxima over the compared ratios, one bound for
         //     every step of the line; a line it does not cover is replayed step by step (the reference's v'
         //     at each step's ratios, the step's own bound) and a step no bound covers is re-decided exactly
         int marg = 0;
         bool detail = false;
         if (on) {
-            const double* vm = p.scr.cut_vmax + ((size_t)b * p.mls_cap + m) * CUT_VMAX;
+            const double* vm = p.scr.cut_vmax + LINE_SLOT(p, b, m) * CUT_VMAX;
             const double mv = vm[4];
             marg = (int)fmod(mv, 1024.0);
             n_eval += (int64_t)(mv / 1024.0);
@@ -3106,15 +3028,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             n_mline += marg ? 1 : 0;
             n_dline += detail ? 1 : 0;
         }
-        VK(4);
+        PHASE_TICK(vk, 4);
         if (detail) {   // to k_cut_verify_detail's list (out of this kernel's register budget); a full list: redo
             const int slot = atomicAdd(p.scr.cut_dtln, 1);
             if (slot < CUT_DTL * p.B) {
-                double* e = p.scr.cut_dtl + (size_t)slot * 32;
+                double* e = p.scr.cut_dtl + (size_t)slot * CUT_DTL_REC;
 #pragma unroll
-                for (int i = 0; i < 21; ++i) e[i] = fr[i][lane];
-                e[21] = K0; e[22] = A1; e[23] = B1; e[24] = cs; e[25] = ce; e[26] = R0; e[27] = rts; e[28] = rte;
-                e[29] = line_ok ? 1.0 : 0.0;
+                for (int i = 0; i < CUT_INFO; ++i) e[DTL_S + i] = fr[i][lane];
+                e[DTL_K0] = K0; e[DTL_A1] = A1; e[DTL_B1] = B1; e[DTL_CS] = cs; e[DTL_CE] = ce; e[DTL_R0] = R0;
+                e[DTL_RTS] = rts; e[DTL_RTE] = rte;
+                e[DTL_OK] = line_ok ? 1.0 : 0.0;
                 p.scr.cut_dtln[1 + slot] = b * p.mls_cap + m;
             } else {
                 bad |= 1024;
@@ -3146,21 +3069,19 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
     if (lane == 0) {
         p.scr.cut_flag[b] = bad;
-        p.scr.bytes[(size_t)STEP_REC * b + 20] = bad;
-        p.scr.bytes[(size_t)STEP_REC * b + 21] = n_marg;
-        p.scr.bytes[(size_t)STEP_REC * b + 22] = n_eval;
-        p.scr.bytes[(size_t)STEP_REC * b + 23] = n_mline;
-        p.scr.dbg[8 * (size_t)b + 4] = mask;
-        p.scr.dbg[8 * (size_t)b + 5] = __double_as_longlong(worst);
-        p.scr.dbg[8 * (size_t)b + 6] = n_xchk;
-        p.scr.dbg[8 * (size_t)b + 7] = n_dline;
-        p.scr.dbg[8 * (size_t)b + 0] = __double_as_longlong(tS);
-        p.scr.dbg[8 * (size_t)b + 1] = __double_as_longlong(tK);
-        p.scr.dbg[8 * (size_t)b + 2] = __double_as_longlong(tA);
-        p.scr.dbg[8 * (size_t)b + 3] = __double_as_longlong(tV);
-#ifdef GFPL_VERIFY_CLOCK
-        for (int i = 0; i < 5; ++i) p.scr.dbg[8 * (size_t)b + i] = (int64_t)vk[i];
-#endif
+        step_rec(p.scr.bytes, b)[GFPL_STEP_PROOF_REDONE] = bad;
+        step_rec(p.scr.bytes, b)[GFPL_STEP_PROOF_STEPS] = n_marg;
+        step_rec(p.scr.bytes, b)[GFPL_STEP_PROOF_VREF] = n_eval;
+        step_rec(p.scr.bytes, b)[GFPL_STEP_PROOF_LINES] = n_mline;
+        dbg_row(p.scr.dbg, b)[DBG_VFY_MASK] = mask;
+        dbg_row(p.scr.dbg, b)[DBG_VFY_WORST] = __double_as_longlong(worst);
+        dbg_row(p.scr.dbg, b)[DBG_VFY_XCHK] = n_xchk;
+        dbg_row(p.scr.dbg, b)[DBG_VFY_DLINES] = n_dline;
+        dbg_row(p.scr.dbg, b)[DBG_VFY_TS] = __double_as_longlong(tS);
+        dbg_row(p.scr.dbg, b)[DBG_VFY_TK] = __double_as_longlong(tK);
+        dbg_row(p.scr.dbg, b)[DBG_VFY_TA] = __double_as_longlong(tA);
+        dbg_row(p.scr.dbg, b)[DBG_VFY_TV] = __double_as_longlong(tV);
+        if (VCLOCK) vk.store(dbg_row(p.scr.dbg, b));   // (over the bound terms)
     }
 }
 
@@ -3172,37 +3093,32 @@ __global__ void __launch_bounds__(64) k_cut_verify_detail(KParams p) {
     for (int i = blockIdx.x * 64 + threadIdx.x; i < n; i += gridDim.x * 64) {
         const int e = p.scr.cut_dtln[1 + i];
         const int b = e / p.mls_cap, m = e % p.mls_cap;
-        const double* pl = p.scr.cut_dtl + (size_t)i * 32;
-        const size_t q = (size_t)b * p.kl_cap + p.tr.matched_ls[(size_t)b * p.mls_cap + m];
-        const double* fd = p.scr.cut_rec + ((size_t)b * p.mls_cap + m) * CUT_REC;
-        const uint8_t* path = p.scr.cut_path + ((size_t)b * p.mls_cap + m) * CUT_PATH;
+        const double* pl = p.scr.cut_dtl + (size_t)i * CUT_DTL_REC;
+        const size_t q = (size_t)b * p.kl_cap + p.tr.matched_ls[LINE_SLOT(p, b, m)];
+        const double* fd = p.scr.cut_rec + LINE_SLOT(p, b, m) * CUT_REC;
+        const uint8_t* path = p.scr.cut_path + LINE_SLOT(p, b, m) * CUT_PATH;
         double Dl[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) Dl[k] = p.scr.cut_dtinv[16 * b + k];
         int nx = 0;
-        const int bad = verify_line_detail(p, Dl, q, path, fd, p.prev.ls.cut[2 * q], p.prev.ls.cut[2 * q + 1], pl[21],
-                                           pl[22], pl[23], pl[24], pl[25], pl[26], pl[27], pl[28], pl[29] != 0.0, pl, 1,
-                                           nx);
+        const int bad = verify_line_detail(p, Dl, q, path, fd, p.prev.ls.cut[2 * q], p.prev.ls.cut[2 * q + 1], pl[DTL_K0],
+                                           pl[DTL_A1], pl[DTL_B1], pl[DTL_CS], pl[DTL_CE], pl[DTL_R0], pl[DTL_RTS],
+                                           pl[DTL_RTE], pl[DTL_OK] != 0.0, pl + DTL_S, 1, nx);
         if (bad) {
             atomicOr(&p.scr.cut_flag[b], 1);
-            atomicOr(reinterpret_cast<unsigned long long*>(&p.scr.bytes[(size_t)STEP_REC * b + 20]), 1ull);
+            atomicOr(reinterpret_cast<unsigned long long*>(&step_rec(p.scr.bytes, b)[GFPL_STEP_PROOF_REDONE]), 1ull);
         }
-        if (nx) atomicAdd(reinterpret_cast<unsigned long long*>(&p.scr.dbg[8 * (size_t)b + 6]), (unsigned long long)nx);
+        if (nx)
+            atomicAdd(reinterpret_cast<unsigned long long*>(&dbg_row(p.scr.dbg, b)[DBG_VFY_XCHK]), (unsigned long long)nx);
     }
 }
 
 // the batch size up to which the one-sequence-per-wave search runs (GFPL_CUT_WAVE_MAX_B overrides:
 // tests run both searches on the same batch)
-static int cut_wave_max_b() {
-    const char* e = getenv("GFPL_CUT_WAVE_MAX_B");
-    return e ? atoi(e) : CUT_WAVE_MAX_B;
-}
+static int cut_wave_max_b() { return env_int("GFPL_CUT_WAVE_MAX_B", CUT_WAVE_MAX_B); }
 
 // the batch size up to which k_cut_prep runs 8 waves per sequence (GFPL_CUT_PREP_W8_MAX_B overrides)
-static int cut_prep_w8_max_b() {
-    const char* e = getenv("GFPL_CUT_PREP_W8_MAX_B");
-    return e ? atoi(e) : 256;
-}
+static int cut_prep_w8_max_b() { return env_int("GFPL_CUT_PREP_W8_MAX_B", 256); }
 
 hipError_t launch_line_cut(const KParams& p, hipStream_t s, const hipEvent_t* marks) {
     const int mode = p.cfg.cut_proof;   // 0 measured, 1 proven (recorded search + verify), 2 eager-proven, 3 (test)

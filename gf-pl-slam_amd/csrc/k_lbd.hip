@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "gfpl_kernels.hpp"
+#include "gfpl_wave.hpp"
 
 namespace gfpl {
 
@@ -41,10 +42,6 @@ struct LbdDev {
 };
 
 namespace {
-__device__ __forceinline__ int refl1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
-// LDS written by some lanes of a wave and read by others: the wave's DS operations complete
-// in order; the clobber keeps the compiler from moving accesses across
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // L5: correctly rounded float sqrt.  __fsqrt_rn lowers to the bare v_sqrt_f32 (1 ulp); the f64
 // sqrt is correctly rounded (N1) and rounding its result to float is exact for sqrt (53 >= 2*24+2)
 __device__ __forceinline__ float sqrt_rn(float x) { return (float)sqrt((double)x); }
@@ -187,7 +184,7 @@ __global__ void __launch_bounds__(256) k_lbd_describe(LbdDev o, const gfpl_keyli
     // per row: pL nL pL2 nL2 pO nO pO2 nO2 (the order of the band statistics below)
     rowv[wave][0][lane] = pl; rowv[wave][1][lane] = nl; rowv[wave][2][lane] = pl * pl; rowv[wave][3][lane] = nl * nl;
     rowv[wave][4][lane] = po; rowv[wave][5][lane] = no; rowv[wave][6][lane] = po * po; rowv[wave][7][lane] = no * no;
-    lds_sync();
+    wave_lds_sync();
     // band sums: statistic s of band b over the rows of bands b-1, b, b+1 in row order
     float bs[2];
 #pragma unroll
@@ -210,13 +207,13 @@ __global__ void __launch_bounds__(256) k_lbd_describe(LbdDev o, const gfpl_keyli
         bs[pass] = acc;
     }
     // band statistic j -> (mean, std) entries of the descriptor vector
-    lds_sync();
+    wave_lds_sync();
     float* D = dv[wave];
     float* S72 = &rowv[wave][0][0];   // the band sums, j = 8 b + s (rows are dead now)
-    lds_sync();
+    wave_lds_sync();
     S72[lane] = bs[0];
     if (lane < 8) S72[64 + lane] = bs[1];
-    lds_sync();
+    wave_lds_sync();
     if (lane < LBD_BANDS * 4) {
         const int b = lane >> 2, k = lane & 3;   // k: pL nL pO nO
         const float invN = (b == 0 || b == LBD_BANDS - 1) ? (float)(1.0 / (LBD_BANDW * 2.0)) : (float)(1.0 / (LBD_BANDW * 3.0));
@@ -225,7 +222,7 @@ __global__ void __launch_bounds__(256) k_lbd_describe(LbdDev o, const gfpl_keyli
         D[8 * b + k] = t;
         D[8 * b + 4 + k] = sqrt_rn(S72[8 * b + s2] * invN - t * t);
     }
-    lds_sync();
+    wave_lds_sync();
     // normalisation (sequential sums in the reference's order), clamp, renormalisation
     float tm = 0.0f, ts = 0.0f;
     for (int b = 0; b < LBD_BANDS; ++b) {
@@ -247,10 +244,10 @@ __global__ void __launch_bounds__(256) k_lbd_describe(LbdDev o, const gfpl_keyli
         }
         e[pass] = v;
     }
-    lds_sync();
+    wave_lds_sync();
     D[lane] = e[0];
     if (lane < 8) D[64 + lane] = e[1];
-    lds_sync();
+    wave_lds_sync();
     float t2 = 0.0f;
     for (int i = 0; i < LBD_BANDS * 8; ++i) t2 += D[i] * D[i];
     t2 = __fdiv_rn(1.0f, sqrt_rn(t2));

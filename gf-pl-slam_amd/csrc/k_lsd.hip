@@ -30,6 +30,7 @@
 #include <cstdio>
 
 #include "gfpl_kernels.hpp"
+#include "gfpl_wave.hpp"
 
 namespace gfpl {
 
@@ -81,20 +82,11 @@ constexpr double k2Pi = 2 * kPi;
 constexpr double kDeg2Rad = kPi / 180;
 
 __device__ __forceinline__ int lane_id() { return __lane_id(); }
-__device__ __forceinline__ void lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // global-memory writes of one lane read by others of the same workgroup: a workgroup-scope
 // fence (the workgroup's waves share the CU's write-through L1; an agent-scope fence would
 // write back / invalidate the L2 every time)
 __device__ __forceinline__ void mem_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
 __device__ __forceinline__ int below(unsigned long long m) { return __popcll(m & ((1ull << lane_id()) - 1ull)); }
-__device__ __forceinline__ double rl_d(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l),
-                            __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ float rl_f(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ int rl_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 __device__ __forceinline__ double wmax(double v) {
     for (int o = 32; o; o >>= 1) v = fmax(v, __shfl_xor(v, o));
     return v;
@@ -102,26 +94,6 @@ __device__ __forceinline__ double wmax(double v) {
 __device__ __forceinline__ double wmin(double v) {
     for (int o = 32; o; o >>= 1) v = fmin(v, __shfl_xor(v, o));
     return v;
-}
-
-// O4: cv::fastAtan2 (degrees)
-__device__ __forceinline__ float fast_atan2(float y, float x) {
-    const float p1 = 0.9997878412794807f * (float)(180 / M_PI), p3 = -0.3258083974640975f * (float)(180 / M_PI),
-                p5 = 0.1555786518463281f * (float)(180 / M_PI), p7 = -0.04432655554792128f * (float)(180 / M_PI);
-    const float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = __fdiv_rn(ay, ax + (float)2.2204460492503131e-16);
-        c2 = c * c;
-        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    } else {
-        c = __fdiv_rn(ax, ay + (float)2.2204460492503131e-16);
-        c2 = c * c;
-        a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    }
-    if (x < 0) a = 180.f - a;
-    if (y < 0) a = 360.f - a;
-    return a;
 }
 
 // S4: fdlibm s_atan.c / e_atan2.c (finite arguments), + - * / only
@@ -197,7 +169,7 @@ __device__ __forceinline__ uint32_t skey(uint64_t e) { return (uint32_t)(e >> 32
 
 template <bool LDS>
 __device__ __forceinline__ void ssync() {
-    if (LDS) lds_sync();
+    if (LDS) wave_lds_sync();
     else mem_sync();
 }
 
@@ -403,9 +375,9 @@ template <int CAP>
 __device__ void flush_small(uint64_t* a, SortLds<CAP>& S, int& ns) {
     const int lane = lane_id();
     if (ns == 0) return;
-    lds_sync();
+    wave_lds_sync();
     if (lane < ns) lane_introsort(a, S.small[3 * lane], S.small[3 * lane + 1], S.small[3 * lane + 2], S.lstk + 9 * lane);
-    lds_sync();
+    wave_lds_sync();
     ns = 0;
 }
 
@@ -438,7 +410,7 @@ __device__ void add_leaf(uint64_t* a, int* leaf, int& nleaf, int f, int l) {
         leaf[2 * nleaf] = f;
         leaf[2 * nleaf + 1] = l - f;
     }
-    lds_sync();
+    wave_lds_sync();
     if (++nleaf == 64) flush_leaves<LDS>(a, leaf, nleaf);
 }
 
@@ -455,7 +427,7 @@ __device__ void introsort_lds(uint64_t* a, int n, int depth, SortLds<CAP>& S, ui
         stk[1] = n;
         stk[2] = depth;
     }
-    lds_sync();
+    wave_lds_sync();
     int sp = 1;
     while (sp > 0) {
         --sp;
@@ -464,7 +436,7 @@ __device__ void introsort_lds(uint64_t* a, int n, int depth, SortLds<CAP>& S, ui
         while (l - f > LSD_SMALL) {
             if (d == 0) {
                 if (lane == 0) heap_sort(a + f, l - f);
-                lds_sync();
+                wave_lds_sync();
                 done = true;
                 break;
             }
@@ -477,7 +449,7 @@ __device__ void introsort_lds(uint64_t* a, int n, int depth, SortLds<CAP>& S, ui
                     stk[3 * sp + 1] = l;
                     stk[3 * sp + 2] = d;
                 }
-                lds_sync();
+                wave_lds_sync();
                 ++sp;
             }
             l = cut;
@@ -488,7 +460,7 @@ __device__ void introsort_lds(uint64_t* a, int n, int depth, SortLds<CAP>& S, ui
                 S.small[3 * ns + 1] = l;
                 S.small[3 * ns + 2] = d;
             }
-            lds_sync();
+            wave_lds_sync();
             if (++ns == 64) flush_small(a, S, ns);
         }
     }
@@ -516,7 +488,7 @@ __device__ void wave_sort(uint64_t* a, int n, int* Lp, int* Rp, SortLdsPair<CAP>
         const int lane = lane_id();
 #pragma unroll 8
         for (int i = lane; i < n; i += 64) P.inner.buf[i] = a[i];
-        lds_sync();
+        wave_lds_sync();
         introsort_lds(P.inner.buf, n, depth, P.inner);
         for (int i = lane; i < n; i += 64) a[i] = P.inner.buf[i];
         mem_sync();
@@ -533,7 +505,7 @@ __device__ void wave_sort(uint64_t* a, int n, int* Lp, int* Rp, SortLdsPair<CAP>
         stk[1] = n;
         stk[2] = depth;
     }
-    lds_sync();
+    wave_lds_sync();
     int sp = 1;
     while (sp > 0) {
         --sp;
@@ -544,7 +516,7 @@ __device__ void wave_sort(uint64_t* a, int n, int* Lp, int* Rp, SortLdsPair<CAP>
                 const int m = l - f;
 #pragma unroll 8
                 for (int i = lane; i < m; i += 64) S.buf[i] = a[f + i];
-                lds_sync();
+                wave_lds_sync();
                 introsort_lds(S.buf, m, d, S);
                 for (int i = lane; i < m; i += 64) a[f + i] = S.buf[i];
                 mem_sync();
@@ -564,7 +536,7 @@ __device__ void wave_sort(uint64_t* a, int n, int* Lp, int* Rp, SortLdsPair<CAP>
                 stk[3 * sp + 1] = l;
                 stk[3 * sp + 2] = d;
             }
-            lds_sync();
+            wave_lds_sync();
             ++sp;
             l = cut;
         }
@@ -668,7 +640,7 @@ __device__ int partition_hoare(uint64_t* a, int f, int l, SortLds<CAP>& S, uint3
         }
         nL = min(nL, BT);
         nR = min(nR, BT);
-        lds_sync();
+        wave_lds_sync();
         const int np = min(nL, nR);
         int kb = 0;   // pairs with L[k] < R[k]: a prefix of the round's ranks
         for (int k0 = 0; k0 < np; k0 += 64) {
@@ -684,7 +656,7 @@ __device__ int partition_hoare(uint64_t* a, int f, int l, SortLds<CAP>& S, uint3
             lbound = (int)RP[BT - 1];
             lnext = rbound + 1;
             rnext = lbound - 1;
-            lds_sync();
+            wave_lds_sync();
             continue;
         }
         // the scans have crossed: L[K] is the next left stopper if this round gathered it (else
@@ -792,7 +764,7 @@ __device__ __forceinline__ void mw_sort(uint64_t* a, int n, int* Lp, int* Rp, So
             if (m <= CAP) {
 #pragma unroll 4
                 for (int i = lane; i < m; i += 64) S.buf[i] = a[f + i];
-                lds_sync();
+                wave_lds_sync();
                 introsort_lds(S.buf, m, d, S, B0);
                 for (int i = lane; i < m; i += 64) a[f + i] = S.buf[i];
                 mem_sync();
@@ -1028,7 +1000,7 @@ struct Used {
         else g[y * W + x] = 0;
     }
     __device__ __forceinline__ void sync() const {
-        if (LU) lds_sync();
+        if (LU) wave_lds_sync();
         else mem_sync();
     }
 };
@@ -1068,8 +1040,8 @@ __device__ int region_grow(const Img& I, const Used<LU>& U, int sx, int sy, uint
     reg_angle = (double)seed_deg * kDeg2Rad;
     float sumdx, sumdy;   // S3
     if (has_pre) {
-        sumdx = rl_f(pcs.x, 25);
-        sumdy = rl_f(pcs.y, 25);
+        sumdx = readlane_f32(pcs.x, 25);
+        sumdy = readlane_f32(pcs.y, 25);
     } else {
         sumdx = (float)det_cos(reg_angle);
         sumdy = (float)det_sin(reg_angle);
@@ -1084,7 +1056,7 @@ __device__ int region_grow(const Img& I, const Used<LU>& U, int sx, int sy, uint
     n = 1;
     bool glob = false;   // (uniform) new points go to the HBM list too
     U.sync();
-    lds_sync();
+    wave_lds_sync();
     // the region list is expanded in batches of up to 7 points: lanes 9g..9g+8 load point
     // i+g's 3x3 neighbour records in one round trip, then the points are processed in list
     // order, each reading the used map as the earlier points of the batch left it
@@ -1139,7 +1111,7 @@ __device__ int region_grow(const Img& I, const Used<LU>& U, int sx, int sy, uint
             unsigned long long m = __ballot(av) >> (9 * k);
             if (!m) continue;
             const int b = 9 * k;
-            const int prx = rl_i(rx, b), pry = rl_i(ry, b);
+            const int prx = readlane_i32(rx, b), pry = readlane_i32(ry, b);
             // isAligned (lsd.cpp) of every pending neighbour against the current reg_angle at
             // once (lane b + t: neighbour t): the first aligned one is the next the serial
             // loop adds, those before it failed against the same angle; the angle then
@@ -1160,18 +1132,18 @@ __device__ int region_grow(const Img& I, const Used<LU>& U, int sx, int sy, uint
                 m &= ~((2ull << t) - 1ull);
                 const int px = prx + t % 3 - 1, py = pry + t / 3 - 1;
                 const uint32_t e = ((uint32_t)py << 16) | (uint32_t)px;
-                const uint32_t pc = LU ? (uint32_t)rl_i((int)cq, b + t) : 0u;
+                const uint32_t pc = LU ? (uint32_t)readlane_i32((int)cq, b + t) : 0u;
                 if (lane == 0) {
                     U.set1(px, py, pc);
                     if (glob) I.reg[n] = e;
                     ring[n & (LSD_RING - 1)] = e;
                 }
                 ++n;
-                sumdx += rl_f(q.y, b + t);
-                sumdy += rl_f(q.z, b + t);
+                sumdx += readlane_f32(q.y, b + t);
+                sumdy += readlane_f32(q.z, b + t);
                 reg_angle = (double)fast_atan2(sumdy, sumdx) * kDeg2Rad;
             }
-            lds_sync();
+            wave_lds_sync();
             if (!LU) mem_sync();
         }
         i += nb;
@@ -1202,9 +1174,9 @@ __device__ void region2rect(const Img& I, int n, double reg_angle, double prec, 
         }
         const int m = min(64, n - b);
         for (int t = 0; t < m; ++t) {
-            X += rl_d(px, t);
-            Y += rl_d(py, t);
-            S += rl_d(w, t);
+            X += readlane_f64(px, t);
+            Y += readlane_f64(py, t);
+            S += readlane_f64(w, t);
         }
     }
     const double x = X / S, y = Y / S;
@@ -1223,9 +1195,9 @@ __device__ void region2rect(const Img& I, int n, double reg_angle, double prec, 
         }
         const int m = min(64, n - b);
         for (int t = 0; t < m; ++t) {
-            Ixx += rl_d(txx, t);
-            Iyy += rl_d(tyy, t);
-            Ixy -= rl_d(txy, t);
+            Ixx += readlane_f64(txx, t);
+            Iyy += readlane_f64(tyy, t);
+            Ixy -= readlane_f64(txy, t);
         }
     }
     const double lambda = 0.5 * (Ixx + Iyy - sqrt((Ixx - Iyy) * (Ixx - Iyy) + 4.0 * Ixy * Ixy));
@@ -1361,7 +1333,7 @@ __device__ bool refine(const Img& I, const Used<LU>& U, int& n, double reg_angle
         const int c = min(64, n - b);
         for (int t = 0; t < c; ++t) {
             if (!((m >> t) & 1ull)) continue;
-            const double v = rl_d(ad, t);
+            const double v = readlane_f64(ad, t);
             sum += v;
             s_sum += v * v;
         }
@@ -1392,7 +1364,7 @@ __device__ void lsd_image(const LsdDev& o, int img, uint32_t* bits, uint32_t* ri
     if (LU) {
         const int nw = (o.ndef[img] + 31) >> 5;
         for (int i = lane; i < nw; i += 64) bits[i] = 0;
-        lds_sync();
+        wave_lds_sync();
     } else {
         for (int i = lane; i < o.W * o.H; i += 64) U.g[i] = 0;
         mem_sync();
@@ -1457,7 +1429,7 @@ __device__ void lsd_image(const LsdDev& o, int img, uint32_t* bits, uint32_t* ri
             if (!mg) break;
             const int j = __ffsll((long long)mg) - 1;
             if (lane <= j) cand = false;
-            const int sx = rl_i(px, j), sy = rl_i(py, j);
+            const int sx = readlane_i32(px, j), sy = readlane_i32(py, j);
             // the next candidate's neighbourhood loads while this region grows (records are
             // static; whether it is still a seed is decided from the used map later)
             const bool has_pre = pre_j == j;
@@ -1468,7 +1440,7 @@ __device__ void lsd_image(const LsdDev& o, int img, uint32_t* bits, uint32_t* ri
             pre_j = m2 ? __ffsll((long long)m2) - 1 : -1;
             pre = make_float4(-1.0f, 0.f, 0.f, 0.f);
             if (pre_j >= 0) {   // (separate registers: no wait for one load before the other)
-                const int cx = rl_i(px, pre_j), cy = rl_i(py, pre_j);
+                const int cx = readlane_i32(px, pre_j), cy = readlane_i32(py, pre_j);
                 const int xx = cx + lane % 5 - 2, yy = cy + lane / 5 - 2;
                 if (lane < 25 && xx >= 0 && yy >= 0 && xx < o.W && yy < o.H) {
                     pre = I.px[yy * o.W + xx];
@@ -1478,8 +1450,8 @@ __device__ void lsd_image(const LsdDev& o, int img, uint32_t* bits, uint32_t* ri
             }
             double reg_angle;
             bool in_hbm;
-            int n = region_grow<LU>(I, U, sx, sy, LU ? (uint32_t)rl_i((int)c0, j) : 0u, rl_f(a0, j), o.prec, reg_angle,
-                                    in_hbm, has_pre, cur, cur_cs, cur_c);
+            int n = region_grow<LU>(I, U, sx, sy, LU ? (uint32_t)readlane_i32((int)c0, j) : 0u, readlane_f32(a0, j), o.prec,
+                                    reg_angle, in_hbm, has_pre, cur, cur_cs, cur_c);
             if (n < o.min_reg_size) continue;
             ring_to_hbm(I, n, in_hbm);
             mem_sync();   // the region list (HBM) is read by every lane next

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "gfpl_kernels.hpp"
+#include "gfpl_wave.hpp"
 #include "gfpl_orb_pattern.h"
 
 namespace gfpl {
@@ -83,9 +84,6 @@ namespace {
 constexpr int kCircleX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
 constexpr int kCircleY[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
 
-// LDS written by some lanes of a wave, then read by others (the wave's DS operations
-// complete in order; the clobber keeps the compiler from moving accesses across)
-__device__ __forceinline__ void wave_sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 #define ORB_MAX_CELLS 4096
 
 __device__ __forceinline__ uint8_t sat_u8(int v) { return (uint8_t)min(max(v, 0), 255); }
@@ -236,7 +234,6 @@ __global__ void __launch_bounds__(RESIZE_T) k_orb_resize(OrbDev o, int l) {
 // thread slides the column pass down 8 rows of one column.
 #define BLUR_TW 64
 #define BLUR_TH 32
-__device__ __forceinline__ int refl1(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 __global__ void __launch_bounds__(256) k_orb_blur(OrbDev o) {
     __shared__ int tile[BLUR_TH + 6][BLUR_TW + 8];   // (dword cells: byte LDS traffic measured slower)
     __shared__ int rows[BLUR_TH + 6][BLUR_TW + 1];
@@ -406,7 +403,7 @@ __device__ __forceinline__ void cell_fast(const uint8_t* P, int pw, uint8_t* Sc,
         if (pass) cand[nc + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)i;
         nc += __popcll(m);
     }
-    wave_sync_lds();
+    wave_lds_sync();
     for (int b = 0; b < nc; b += 64) {
         if (b + lane < nc) {
             const int i = cand[b + lane];
@@ -502,14 +499,14 @@ __global__ void __launch_bounds__(256) k_orb_cellfast(OrbDev o) {
             if (idx < pw * ph) P[idx] = v[q];
         }
     }
-    wave_sync_lds();
+    wave_lds_sync();
     uint32_t* K = o.ckeys + ((size_t)img * o.ncell + c) * o.ccap;
     cell_fast(P, pw, Sc, cand, dw, dh, o.ini_th, lane);
-    wave_sync_lds();
+    wave_lds_sync();
     int pos = cell_nms(Sc, dw, dh, K, o.ccap, iniX + 3 - L.minBX, iniY + 3 - L.minBY, lane);
     if (pos == 0) {   // vKeysCell.empty(): FAST again at minThFAST (:803-808)
         cell_fast(P, pw, Sc, cand, dw, dh, o.min_th, lane);
-        wave_sync_lds();
+        wave_lds_sync();
         pos = cell_nms(Sc, dw, dh, K, o.ccap, iniX + 3 - L.minBX, iniY + 3 - L.minBY, lane);
     }
     if (lane == 0) {
@@ -685,7 +682,7 @@ __global__ void __launch_bounds__(64) k_orb_octree(OrbDev o) {
     // non-empty children pushed to the front in n1..n4 order, those with > 1 keys recorded,
     // the parent erased.  Returns the number recorded.
     auto divide = [&](int i) -> int {
-        wave_sync_lds();
+        wave_lds_sync();
         const ONode nv = nd[i];
         const int x0 = nv.x0, y0 = nv.y0, x1 = nv.x1, y1 = nv.y1, off = nv.off, len = nv.len;
         int pv = nv.prev;
@@ -820,7 +817,7 @@ __global__ void __launch_bounds__(64) k_orb_octree(OrbDev o) {
             }
         }
     }
-    wave_sync_lds();
+    wave_lds_sync();
     // ---- the subdivision loop (:594-739), one call site of divide (code size): phase 0 =
     // the first pass, 1 = a later pass of the main loop, 2 = a round of the sorted expansion
     // (:699-737).  Each pass / round reads its work list `prv` from the back and records
@@ -835,7 +832,7 @@ __global__ void __launch_bounds__(64) k_orb_octree(OrbDev o) {
         } else {
             // vPrevSizeAndPointerToNode = vSizeAndPointerToNode sorted by (size, node) (O6):
             // rank sort (the entries are distinct) from cur into prv
-            wave_sync_lds();
+            wave_lds_sync();
             for (int e = lane; e < ntodo; e += 64) {
                 const OExp v = cur[e];
                 int rank = 0;
@@ -843,7 +840,7 @@ __global__ void __launch_bounds__(64) k_orb_octree(OrbDev o) {
                 prv[rank] = v;
             }
         }
-        wave_sync_lds();
+        wave_lds_sync();
         ncur = 0;
         int nToExpand = 0;
         for (int j = ntodo - 1; j >= 0; --j) {
@@ -855,7 +852,7 @@ __global__ void __launch_bounds__(64) k_orb_octree(OrbDev o) {
         if (lsize >= N || lsize == prevSize) finish = true;
         else if (phase < 2) phase = (lsize + nToExpand * 3 > N) ? 2 : 1;
     }
-    wave_sync_lds();
+    wave_lds_sync();
     // ---- the best key of every node, in list order (:741-760): first strict maximum.
     // The list order into LDS (prv is free now), then a lane per node for nodes of up to
     // 16 keys and the whole wave for the larger ones
@@ -864,7 +861,7 @@ __global__ void __launch_bounds__(64) k_orb_octree(OrbDev o) {
         int k = 0;
         for (int it = head; it >= 0; it = nd[it].next) ordl[k++] = (int16_t)it;
     }
-    wave_sync_lds();
+    wave_lds_sync();
     const int n_out = lsize;
     for (int base = 0; base < n_out; base += 64) {
         const int idx = base + lane;
@@ -906,26 +903,6 @@ __global__ void __launch_bounds__(64) k_orb_octree(OrbDev o) {
 }
 
 // ----------------------------------------------------------------- describe --
-// O4: cv::fastAtan2 (degrees)
-__device__ __forceinline__ float fast_atan2(float y, float x) {
-    const float p1 = 0.9997878412794807f * (float)(180 / M_PI), p3 = -0.3258083974640975f * (float)(180 / M_PI),
-                p5 = 0.1555786518463281f * (float)(180 / M_PI), p7 = -0.04432655554792128f * (float)(180 / M_PI);
-    const float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = __fdiv_rn(ay, ax + (float)2.2204460492503131e-16);
-        c2 = c * c;
-        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    } else {
-        c = __fdiv_rn(ax, ay + (float)2.2204460492503131e-16);
-        c2 = c * c;
-        a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    }
-    if (x < 0) a = 180.f - a;
-    if (y < 0) a = 360.f - a;
-    return a;
-}
-
 // two kept keypoints per wave (one per 32-lane half, 8 per workgroup): IC_Angle's integer
 // moments over the 31-px disc split across the half's lanes (u = lane - 15, rows v = 0..15)
 // and reduced (exact in any order); bit 32w + lane of the descriptor (pattern points 2b,

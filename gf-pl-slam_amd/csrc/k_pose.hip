@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "gfpl_kernels.hpp"
+#include "gfpl_wave.hpp"
 
 namespace gfpl {
 
@@ -41,7 +42,8 @@ __device__ __forceinline__ void pose_bar() {
     }
 }
 
-struct PoseLDS {
+// (-DGFPL_POSE_CLOCK: wave 0's shader-clock cycles per phase, ticked by k_pose and gauss_newton)
+struct PoseLDS : PhaseClock<GFPL_DIAG(GFPL_POSE_CLOCK), 8> {
     double DT[16];
     double DTini[16];
     double H[36];     // (the reduction partials, the increment and se3_update_wave's scratch live
@@ -54,15 +56,7 @@ struct PoseLDS {
     int cmd, c0, np_act, nl_act, nch;   // k_pose<W > 1>: helper command (0 exit, 1 evaluate chunks c0 + w)
     int pcomp, lcomp;                   // k_pose<W > 1>: the run reads the compacted records (pose_act)
     int gen;                            // k_pose<W > 1>: GN run number (the helpers' register-held inputs)
-#ifdef GFPL_POSE_CLOCK   // (diagnostic build: wave 0's shader-clock cycles per phase, scr.dbg 0-7)
-    unsigned long long ck[8], ck0;
-#endif
 };
-#ifdef GFPL_POSE_CLOCK
-#define POSE_CK(S, i) do { if (threadIdx.x == 0) { const unsigned long long t_ = clock64(); (S).ck[i] += t_ - (S).ck0; (S).ck0 = t_; } } while (0)
-#else
-#define POSE_CK(S, i) do { } while (0)
-#endif
 
 // DT <- DT * inverse_se3(expmap_se3(inc)) (gaussNewtonOptimization, src/stereoFrameHandler.cpp:
 // 2046-2050) by the wave, element-parallel: every element is formed by the expression the serial
@@ -377,7 +371,7 @@ __device__ void gauss_newton(const KParams& p, const PoseCtx& X, PoseLDS& S, dou
     double* part = cp;        // [64] the 28 + 28 reduction partials
     double* incs = cp + 64;   // [6] the increment
     double* xs = cp + 72;     // [48] se3_update_wave scratch
-    POSE_CK(S, 7);
+    if (threadIdx.x == 0) PHASE_TICK(S, 7);
     for (int it = 0; it < max_iters; ++it) {
         pose_prio(stage, it, max_iters);
         // the evaluations read DT from LDS (wave-uniform broadcast reads) instead of
@@ -440,7 +434,7 @@ __device__ void gauss_newton(const KParams& p, const PoseCtx& X, PoseLDS& S, dou
                 __syncthreads();   // (A) the helpers read the command, DT and the positions
                 pose_eval_chunk<W>(p, pa, la, S.DT, c0, np_act, nl_act, cp, cl, 0, pv0, lv0, !(KEEP && nch <= W && it > 0));
                 __syncthreads();   // (B) the round's rows are in LDS
-                POSE_CK(S, 5);
+                if (threadIdx.x == 0) PHASE_TICK(S, 5);
                 const int nw = min(W, nch - c0);
                 for (int wb = 0; wb < nw; ++wb) {
                     const double* bw = (list == 0 ? cp : cl) + wb * (16 * CH_STRIDE);
@@ -469,7 +463,7 @@ __device__ void gauss_newton(const KParams& p, const PoseCtx& X, PoseLDS& S, dou
             }
             pose_bar<W>();
         }
-        POSE_CK(S, 1);
+        if (threadIdx.x == 0) PHASE_TICK(S, 1);
         part[lane] = s;
         pose_bar<W>();
         // H = H_p + H_l, one element per lane (the symmetric pair gets the same sum)
@@ -503,9 +497,9 @@ __device__ void gauss_newton(const KParams& p, const PoseCtx& X, PoseLDS& S, dou
             S.upd = upd;
         }
         pose_bar<W>();
-        POSE_CK(S, 2);
+        if (threadIdx.x == 0) PHASE_TICK(S, 2);
         if (S.upd) se3_update_wave<W>(incs, S.DT, xs);   // DT * inverse_se3(expmap_se3(inc)), before the nrm break
-        POSE_CK(S, 3);
+        if (threadIdx.x == 0) PHASE_TICK(S, 3);
         if (S.brk) break;
     }
 }
@@ -560,13 +554,8 @@ __device__ double stdv_mad(double* buf, int n, int NP2) {
 // sqrt(.) * sqrt(sigma2) and fabsf(.) are never -0.0.
 template <typename K>
 __device__ __forceinline__ K readlane_key(K v, int l) {
-    if (sizeof(K) == 8) {
-        const uint64_t u = (uint64_t)v;
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, l);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), l);
-        return (K)(((uint64_t)hi << 32) | lo);
-    }
-    return (K)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+    if (sizeof(K) == 8) return (K)readlane_u64((uint64_t)v, l);
+    return (K)(uint32_t)readlane_i32((int)(uint32_t)v, l);
 }
 template <typename K, int R>
 __device__ __forceinline__ K wave_select(const K* key, int n, int k) {
@@ -624,12 +613,6 @@ __device__ __forceinline__ double stdv_mad_regs(const double* r, int n) {
     return 1.4826 * mad;
 }
 #define POSE_MAD_R 8   // residuals per lane held in registers (lists of up to 512 entries)
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // removeOutliers(DT_) (:2058-2116): the residual of list entry k (its record in pose_in)
 __device__ __forceinline__ double point_residual(const KParams& p, const double* pin, const double* DTs, int k) {
@@ -718,10 +701,7 @@ __global__ void __launch_bounds__(64 * W, W == 1 ? GFPL_POSE_WAVES : 1) k_pose(K
         S.DT[lane] = S.DTini[lane];
     }
     if (lane == 0) { S.ninl = p.tr.n_inliers[b]; S.gen = 0; }
-#ifdef GFPL_POSE_CLOCK
-    if (lane < 8) S.ck[lane] = 0;
-    if (lane == 0) S.ck0 = clock64();
-#endif
+    if (lane == 0) S.reset();
     // gather the matched lists once (lane l owns positions l, l+64, ...)
     int cpn = 0, cln = 0;
     for (int f = lane; f < npt; f += 64) {
@@ -744,12 +724,12 @@ __global__ void __launch_bounds__(64 * W, W == 1 ? GFPL_POSE_WAVES : 1) k_pose(K
     cln = wave_sum(cln);
     if (lane == 0) { S.cnt[0] = cpn; S.cnt[1] = cln; }
     pose_bar<W>();
-    POSE_CK(S, 0);
+    if (threadIdx.x == 0) PHASE_TICK(S, 0);
     int ok = 0;        // 1: stage-2 DT usable
     double err = 0.0;  // err of the last GN run (reference: uninitialised when no GN runs, pinned 0)
     if (S.ninl > p.cfg.min_features) {
         gauss_newton<W>(p, X, S, cp, cl, p.cfg.max_iters, 0);
-        POSE_CK(S, 7);
+        if (threadIdx.x == 0) PHASE_TICK(S, 7);
         err = S.err;
         double DTs[16];
         for (int i = 0; i < 16; ++i) DTs[i] = S.DT[i];
@@ -812,7 +792,7 @@ __global__ void __launch_bounds__(64 * W, W == 1 ? GFPL_POSE_WAVES : 1) k_pose(K
                 S.cnt[0] = ap; S.cnt[1] = al;
             }
             pose_bar<W>();
-            POSE_CK(S, 4);
+            if (threadIdx.x == 0) PHASE_TICK(S, 4);
             if (S.ninl > p.cfg.min_features) {
                 if (lane < 16) S.DT[lane] = S.DTini[lane];   // Q3: stage 2 restarts from DT_ini
                 pose_bar<W>();
@@ -822,14 +802,12 @@ __global__ void __launch_bounds__(64 * W, W == 1 ? GFPL_POSE_WAVES : 1) k_pose(K
             }
         }
     }
-    POSE_CK(S, 7);
+    if (threadIdx.x == 0) PHASE_TICK(S, 7);
     if (W > 1) {   // release the helpers
         if (lane == 0) S.cmd = 0;
         __syncthreads();
     }
-#ifdef GFPL_POSE_CLOCK
-    if (lane < 8) p.scr.dbg[8 * (size_t)b + lane] = (int64_t)S.ck[lane];
-#endif
+    if (lane == 0) S.store(dbg_row(p.scr.dbg, b));
     if (lane == 0) {
         for (int i = 0; i < 16; ++i) p.scr.pose_DT[16 * b + i] = S.DT[i];
         for (int i = 0; i < 36; ++i) p.scr.pose_H[36 * b + i] = S.H[i];
@@ -847,10 +825,10 @@ __global__ void __launch_bounds__(64 * W, W == 1 ? GFPL_POSE_WAVES : 1) k_pose(K
 __global__ void __launch_bounds__(128) k_pose_finish(KParams p) {
     const int b = blockIdx.x * 64 + (threadIdx.x & 63), role = threadIdx.x >> 6;
     if (b >= p.B) return;
-#ifdef GFPL_PFIN_CLOCK
-    const uint64_t pf0 = clock64();
-#endif
-    if (role == 0) p.scr.bytes[(size_t)STEP_REC * b + 18] = p.tr.n_inliers[b];   // inliers after removeOutliers (step record)
+    // (-DGFPL_PFIN_CLOCK: cycles of H^-1, the eigenvalues (wave 1), the rest (wave 0): DbgPoseFinish)
+    PhaseClock<GFPL_DIAG(GFPL_PFIN_CLOCK), 3> pf;
+    pf.reset();
+    if (role == 0) step_rec(p.scr.bytes, b)[GFPL_STEP_INLIERS_POSE] = p.tr.n_inliers[b];   // (after removeOutliers)
     DevPose& CP = p.curr.pose;
     const DevPose& PP = p.prev.pose;
     const int ok = p.scr.pose_ok[b];
@@ -869,16 +847,12 @@ __global__ void __launch_bounds__(128) k_pose_finish(KParams p) {
 #pragma unroll
         for (int i = 0; i < 36; ++i) DT_cov[i] = 0.0;
     }
-#ifdef GFPL_PFIN_CLOCK
-    const uint64_t pf1 = clock64();
-#endif
+    pf.tick(DBG_PFIN_INVERSE);
     if (role == 1) {
         double eig[6];
         eig_sym<6>(DT_cov, eig);
-#ifdef GFPL_PFIN_CLOCK
-        p.scr.dbg[8 * (size_t)b + 1] = (int64_t)(clock64() - pf1);
-        p.scr.dbg[8 * (size_t)b + 0] = (int64_t)(pf1 - pf0);
-#endif
+        pf.tick(DBG_PFIN_EIG);
+        pf.store(dbg_row(p.scr.dbg, b), DBG_PFIN_INVERSE, 2);
 #pragma unroll
         for (int i = 0; i < 6; ++i) CP.DT_cov_eig[6 * b + i] = eig[i];
         return;
@@ -922,9 +896,8 @@ __global__ void __launch_bounds__(128) k_pose_finish(KParams p) {
 #pragma unroll
     for (int i = 0; i < 36; ++i) { CP.DT_cov[36 * b + i] = DT_cov[i]; CP.Tfw_cov[36 * b + i] = Tcov[i]; }
     CP.err_norm[b] = err_norm;
-#ifdef GFPL_PFIN_CLOCK
-    p.scr.dbg[8 * (size_t)b + 2] = (int64_t)(clock64() - pf1);
-#endif
+    pf.tick(DBG_PFIN_REST);
+    pf.store(dbg_row(p.scr.dbg, b) + DBG_PFIN_REST, DBG_PFIN_REST, 1);
 }
 
 // needNewKF (src/stereoFrameHandler.cpp:2309-2349), one lane per sequence, on the
@@ -1009,19 +982,13 @@ hipError_t launch_curr_frame_is_kf(const KParams& p, const int32_t* mask, hipStr
 #define POSE_MULTI_MAX_B 1024
 #endif
 // the batch size up to which k_pose runs POSE_W waves per sequence (GFPL_POSE_MULTI_MAX_B overrides)
-static int pose_multi_max_b() {
-    const char* e = getenv("GFPL_POSE_MULTI_MAX_B");
-    return e ? atoi(e) : POSE_MULTI_MAX_B;
-}
+static int pose_multi_max_b() { return env_int("GFPL_POSE_MULTI_MAX_B", POSE_MULTI_MAX_B); }
 // ... and up to which it runs 8 (a list of <= 512 active entries is then one round of chunks per GN
 // iteration; 1 workgroup of 8 waves per CU at B <= 256); GFPL_POSE_W8_MAX_B overrides
 #ifndef POSE_W8_MAX_B
 #define POSE_W8_MAX_B 256
 #endif
-static int pose_w8_max_b() {
-    const char* e = getenv("GFPL_POSE_W8_MAX_B");
-    return e ? atoi(e) : POSE_W8_MAX_B;
-}
+static int pose_w8_max_b() { return env_int("GFPL_POSE_W8_MAX_B", POSE_W8_MAX_B); }
 
 hipError_t launch_pose(const KParams& p, hipStream_t s, hipEvent_t mark) {
     int NP2 = 1;

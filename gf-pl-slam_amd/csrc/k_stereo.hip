@@ -14,6 +14,7 @@
 
 #include "gfpl_kernels.hpp"
 #include "gfpl_knn.hpp"
+#include "gfpl_wave.hpp"
 
 namespace gfpl {
 
@@ -218,9 +219,6 @@ __device__ __forceinline__ void sad_finish(const KParams& p, const SadJob& J, fl
 #define GFPL_SP_TX 6
 #endif
 
-// LDS-only wave sync: the wave's earlier LDS writes / reads have completed (LDS executes a
-// wave's accesses in order; the clobber keeps the compiler from moving accesses across it)
-__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // dynamic LDS: StereoPointsLds (gfpl_layout.hpp)
 // Right keypoints are sorted by their row band start (the reference's
 // vRowIndices buckets, src/stereoFrame.cpp:459-485) and their x, octave and band
@@ -247,11 +245,6 @@ __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcn
 #else
 #define SP_PRIO(k) do { } while (0)
 #endif
-#ifdef GFPL_SP_CLOCK
-#define SP_CLK(k) do { if (threadIdx.x == 0) p.scr.dbg[8 * (size_t)blockIdx.x + (k)] = (int64_t)wall_clock64(); } while (0)
-#else
-#define SP_CLK(k) do { } while (0)
-#endif
 template <int BLOCK, bool SEG>
 __global__ void __launch_bounds__(BLOCK, GFPL_SP_WAVES) k_stereo_points(KParams p, int KP2) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -266,7 +259,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SP_WAVES) k_stereo_points(KParams 
     int* const misc = S.misc;
     const int NBIN = S.nbin, nrl = S.nrl;
     const int tid = threadIdx.x;
-    SP_CLK(0);
+    DIAG_STAMP(GFPL_SP_CLOCK, threadIdx.x == 0, dbg_row(p.scr.dbg, blockIdx.x), 0);
     SP_PRIO(3);
     const int N = min(p.in.n_kp_l[b], cap), Nr = min(p.in.n_kp_r[b], cap);
     const gfpl_keypoint* KL = p.in.kp_l + (size_t)b * cap;
@@ -408,7 +401,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SP_WAVES) k_stereo_points(KParams 
     }
     __syncthreads();
     }
-    SP_CLK(1);
+    DIAG_STAMP(GFPL_SP_CLOCK, threadIdx.x == 0, dbg_row(p.scr.dbg, blockIdx.x), 1);
     SP_PRIO(2);
     // SEG: first candidate of segment o for a row: the first bin with minr >= row - D_o
     auto seg_start = [&](int o, int row) {
@@ -530,7 +523,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SP_WAVES) k_stereo_points(KParams 
                 uint32_t xk = best;
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) xk ^= __shfl_xor(xk, o);
-                if (lane == 0) p.scr.dbg[8 * (size_t)b + 7] += (int64_t)xk;
+                if (lane == 0) dbg_row(p.scr.dbg, b)[DBG_SP_PROBE_KEYS] += (int64_t)xk;
             }
 #endif
             if (t < N) finish_kp(t, iL, kpL, bestDist, bestIdxR);
@@ -574,7 +567,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SP_WAVES) k_stereo_points(KParams 
     }
     }
     __syncthreads();
-    SP_CLK(2);
+    DIAG_STAMP(GFPL_SP_CLOCK, threadIdx.x == 0, dbg_row(p.scr.dbg, blockIdx.x), 2);
     SP_PRIO(1);
     // SEG: the SAD jobs counting-sorted by the tile of their window — (level, 8-row band,
     // 64-px column strip), coarser on large images so the tiles fit 4096 bins — so the 16 quads
@@ -631,7 +624,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SP_WAVES) k_stereo_points(KParams 
         for (int r = 0; r < RMAX; ++r)
             if (jb[r] != 0xFFFFFFFFu) sj[(int)off[jr[r] & 0xFFFFu] + (int)(jr[r] >> 16)] = jb[r];
         __syncthreads();
-        SP_CLK(3);
+        DIAG_STAMP(GFPL_SP_CLOCK, threadIdx.x == 0, dbg_row(p.scr.dbg, blockIdx.x), 3);
         jobs = sj;
     }
     // sub-pixel refinement + disparity gate (src/stereoFrame.cpp:547-583), one DPP quad
@@ -684,7 +677,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SP_WAVES) k_stereo_points(KParams 
         }
     }
     __syncthreads();
-    SP_CLK(4);
+    DIAG_STAMP(GFPL_SP_CLOCK, threadIdx.x == 0, dbg_row(p.scr.dbg, blockIdx.x), 4);
     SP_PRIO(0);
     // sort(vDistIdx) (src/stereoFrame.cpp:585): the (dist, iL) keys ascending
     uint32_t* keys = pairs;
@@ -810,7 +803,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SP_WAVES) k_stereo_points(KParams 
         p.curr.pose.time_stamp[b] = p.in.time_stamp[b];
         p.scr.n_subpix[b] = misc[2];
     }
-    SP_CLK(5);
+    DIAG_STAMP(GFPL_SP_CLOCK, threadIdx.x == 0, dbg_row(p.scr.dbg, blockIdx.x), 5);
 }
 
 // ------------------------------------------------------- stereo lines --
@@ -938,11 +931,6 @@ __device__ void write_line(const KParams& p, DevLines& C, size_t q, const LineOu
 // 2000 lines per side (config 5) fit.
 // diagnostic build (-DGFPL_SL_CLOCK): the phase boundaries' wall clock per sequence (scr.dbg): start,
 // train rows staged, knn pass, medians, end (tools/sp_phases.py --lines)
-#ifdef GFPL_SL_CLOCK
-#define SL_CLK(k) do { if (threadIdx.x == 0 && !INITIAL) p.scr.dbg[8 * (size_t)blockIdx.x + (k)] = (int64_t)wall_clock64(); } while (0)
-#else
-#define SL_CLK(k) do { } while (0)
-#endif
 template <int CELL, bool INITIAL, int BLOCK>
 __global__ void __launch_bounds__(BLOCK, GFPL_SL_WAVES) k_stereo_lines(KParams p) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -969,19 +957,19 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SL_WAVES) k_stereo_lines(KParams p
     }
     const uint8_t* DLg = p.in.ldesc_l + (size_t)b * cap * 32;
     const uint8_t* DRg = p.in.ldesc_r + (size_t)b * cap * 32;
-    SL_CLK(0);
+    DIAG_STAMP(GFPL_SL_CLOCK, threadIdx.x == 0 && !INITIAL, dbg_row(p.scr.dbg, blockIdx.x), 0);
     SL_PRIO(3);   // issue priority by phase (as k_stereo_points: the last-dispatched workgroups keep up)
     knn_stage_views<CELL>(tb, cap, DRg, NR);
     for (int i = tid; i < 260; i += blockDim.x) hist[i] = 0;
     for (int j = tid; j < NR; j += blockDim.x) rl_i[j] = -1;   // R->L keys (atomicMin)
     knn_lut_fill<CELL>(lut);
     __syncthreads();
-    SL_CLK(1);
+    DIAG_STAMP(GFPL_SL_CLOCK, threadIdx.x == 0 && !INITIAL, dbg_row(p.scr.dbg, blockIdx.x), 1);
     // L->R knn-2 on the matrix cores (gfpl_knn.hpp): keys (dist << 16 | iR); the R->L knn
     // (only its best index is used) from the same distance tiles
     knn2_mfma<CELL>(tb, cap, NR, DLg, NL, (uint32_t*)lr_i, (uint32_t*)lr_d1, (uint32_t*)rl_i);
     __syncthreads();
-    SL_CLK(2);
+    DIAG_STAMP(GFPL_SL_CLOCK, threadIdx.x == 0 && !INITIAL, dbg_row(p.scr.dbg, blockIdx.x), 2);
     SL_PRIO(1);
     for (int i = tid; i < NL; i += blockDim.x) {
         const uint32_t k0 = (uint32_t)lr_i[i], k1 = (uint32_t)lr_d1[i];
@@ -1000,7 +988,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SL_WAVES) k_stereo_lines(KParams p
     }
     __syncthreads();
     const double nn12_dist_th = reinterpret_cast<double*>(misc + 8)[0];
-    SL_CLK(3);
+    DIAG_STAMP(GFPL_SL_CLOCK, threadIdx.x == 0 && !INITIAL, dbg_row(p.scr.dbg, blockIdx.x), 3);
     const int n_matches = min(NL, NR);   // Q5
     const gfpl_keyline* KL = p.in.kl_l + (size_t)b * cap;
     const gfpl_keyline* KR = p.in.kl_r + (size_t)b * cap;
@@ -1023,7 +1011,7 @@ __global__ void __launch_bounds__(BLOCK, GFPL_SL_WAVES) k_stereo_lines(KParams p
         off += tot;
     }
     if (tid == 0) C.n[b] = off;
-    SL_CLK(4);
+    DIAG_STAMP(GFPL_SL_CLOCK, threadIdx.x == 0 && !INITIAL, dbg_row(p.scr.dbg, blockIdx.x), 4);
 }
 
 // -------------------------------------------------- initial-frame points --
@@ -1142,9 +1130,7 @@ __global__ void __launch_bounds__(256) k_line_uncertainty(KParams p) {
 
 // Algorithmic HBM bytes of one step of one sequence, per stage (DESIGN.md
 // §Roofline): the bytes each stage must read or write at minimum, from the
-// runtime counts.  bytes[b*STEP_REC + s], s = 0 stereo_points, 1 stereo_lines,
-// 2 cross_points (+ prev line uncertainty), 3 cross_lines, 4 line_cut, 5 pose,
-// 6 total, 7 k_cut_search; 8-15 the counts they are priced on.
+// runtime counts, into the sequence's step record (GFPL_STEP_*, gfpl_records.hpp).
 __global__ void k_step_bytes(KParams p) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= p.B) return;
@@ -1162,22 +1148,25 @@ __global__ void k_step_bytes(KParams p) {
     st[4] = 608 * Ml + 44 * Mp;                              // cut: line/point info inputs, cut endpoints + invCov
     st[5] = 54 * Mp + 86 * Ml + 1504;                        // GN inputs once, inlier flags, pose + covariances
     int64_t tot = 0;
-    int64_t* rec = p.scr.bytes + (size_t)STEP_REC * b;
-    for (int i = 0; i < 6; ++i) { rec[i] = st[i]; tot += st[i]; }
-    rec[6] = tot;
+    int64_t* rec = step_rec(p.scr.bytes, b);
+    for (int i = 0; i < 6; ++i) { rec[GFPL_STEP_B_STEREO_POINTS + i] = st[i]; tot += st[i]; }
+    rec[GFPL_STEP_B_TOTAL] = tot;
     // k_cut_search alone: per matched line its cut inputs (sP eP covS covE le_obs
     // 208 B + index 4 B), its r = 0 info from k_cut_prep (168 B), the cut ratio
     // written (16 B); per sequence invCov_sum + metric + DT_inv (272 B)
-    rec[7] = (p.cfg.use_line_conf_cut && Ml > 0) ? 396 * Ml + 272 : 0;
+    rec[GFPL_STEP_B_CUT_SEARCH] = (p.cfg.use_line_conf_cut && Ml > 0) ? 396 * Ml + 272 : 0;
     // the counts the bytes are priced on (the bench's per-step means)
-    rec[8] = No; rec[9] = Nk; rec[10] = Mo; rec[11] = Sp2; rec[12] = Sl2; rec[13] = Mp; rec[14] = Ml;
-    rec[15] = p.tr.n_inliers[b];
-    if (!(p.cfg.use_line_conf_cut && Ml > 0)) rec[16] = rec[17] = 0;   // k_cut_search writes them otherwise
-    rec[18] = rec[15];   // until optimize_pose (k_pose_finish) records its inliers
-    if (!(p.cfg.use_line_conf_cut && Ml > 0)) rec[19] = 0;   // k_cut_search writes it otherwise
-    // 20-23: the proven line cut's counts (k_cut_verify, cut_proof 1 / 3); zero for a step without it
+    rec[GFPL_STEP_N_O] = No; rec[GFPL_STEP_N_K] = Nk; rec[GFPL_STEP_M_O] = Mo; rec[GFPL_STEP_S_P] = Sp2;
+    rec[GFPL_STEP_S_L] = Sl2; rec[GFPL_STEP_M_P] = Mp; rec[GFPL_STEP_M_L] = Ml;
+    rec[GFPL_STEP_N_INLIERS] = p.tr.n_inliers[b];
+    // (k_cut_search writes its slots otherwise)
+    if (!(p.cfg.use_line_conf_cut && Ml > 0)) rec[GFPL_STEP_CUT_STEPS] = rec[GFPL_STEP_CUT_EXACT] = 0;
+    rec[GFPL_STEP_INLIERS_POSE] = rec[GFPL_STEP_N_INLIERS];   // until optimize_pose (k_pose_finish) records its inliers
+    if (!(p.cfg.use_line_conf_cut && Ml > 0)) rec[GFPL_STEP_CUT_UNBOUNDED] = 0;
+    // the proven line cut's counts (k_cut_verify, cut_proof 1 / 3); zero for a step without it
     if (!(p.cfg.use_line_conf_cut && p.cfg.cut_with_max_vol && (p.cfg.cut_proof == 1 || p.cfg.cut_proof == 3)))
-        rec[20] = rec[21] = rec[22] = rec[23] = 0;
+        rec[GFPL_STEP_PROOF_REDONE] = rec[GFPL_STEP_PROOF_STEPS] = rec[GFPL_STEP_PROOF_VREF] =
+            rec[GFPL_STEP_PROOF_LINES] = 0;
     // insertStereoPair's last statement, numFrameSinceKeyframe++ (src/stereoFrameHandler.cpp:150):
     // this per-sequence kernel closes every gfpl_insert_stereo_pair
     p.tr.kf_nsince[b] = p.tr.kf_nsince[b] + 1;
@@ -1191,10 +1180,7 @@ static inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p;
 #ifndef SP_WIDE_MAX_B
 #define SP_WIDE_MAX_B 256
 #endif
-int sp_wide_max_b() {
-    const char* e = getenv("GFPL_SP_WIDE_MAX_B");
-    return e ? atoi(e) : SP_WIDE_MAX_B;
-}
+int sp_wide_max_b() { return env_int("GFPL_SP_WIDE_MAX_B", SP_WIDE_MAX_B); }
 
 hipError_t launch_stereo_points(const KParams& p, hipStream_t s) {
     const int KP2 = next_pow2(p.kp_cap);

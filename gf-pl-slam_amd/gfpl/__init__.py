@@ -13,6 +13,7 @@ tests read like the reference's own call sequence (app/plslam_mod.cpp:375-477):
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import json
 import os
 from typing import Optional
@@ -33,6 +34,38 @@ HAMMING, HAMMING2 = 1, 2
 ERRORS = {0: "ok", -1: "invalid argument", -2: "HIP runtime error", -3: "no HIP device",
           -4: "knn-2 needs at least 2 train descriptors", -5: "capacity exceeded",
           -6: "call order violated", -7: "unsupported config", -8: "device memory allocation failed"}
+
+
+class StepSlot(enum.IntEnum):
+    """Slots of a sequence's step record (``debug_step_records``): the GFPL_STEP_* constants of
+    include/gfpl.h, member for member (tests/test_abi.py compares them)."""
+    B_STEREO_POINTS = 0
+    B_STEREO_LINES = 1
+    B_CROSS_POINTS = 2
+    B_CROSS_LINES = 3
+    B_LINE_CUT = 4
+    B_POSE = 5
+    B_TOTAL = 6
+    B_CUT_SEARCH = 7
+    N_O = 8
+    N_K = 9
+    M_O = 10
+    S_P = 11
+    S_L = 12
+    M_P = 13
+    M_L = 14
+    N_INLIERS = 15
+    CUT_STEPS = 16
+    CUT_EXACT = 17
+    INLIERS_POSE = 18
+    CUT_UNBOUNDED = 19
+    PROOF_REDONE = 20
+    PROOF_STEPS = 21
+    PROOF_VREF = 22
+    PROOF_LINES = 23
+
+
+STEP_REC = len(StepSlot)
 
 
 class GfplError(RuntimeError):
@@ -1074,8 +1107,9 @@ class StereoFrameHandler:
         return out
 
     def debug_step_records(self) -> np.ndarray:
-        """gfpl_debug_step_records: every sequence's record of the last step [B][24] (int64)."""
-        out = np.zeros((self.B, 24), np.int64)
+        """gfpl_debug_step_records: every sequence's record of the last step [B][STEP_REC] (int64),
+        columns StepSlot."""
+        out = np.zeros((self.B, STEP_REC), np.int64)
         check(self.L.gfpl_debug_step_records(self.h, out.ctypes.data), "debug_step_records")
         return out
 

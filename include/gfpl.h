@@ -741,14 +741,45 @@ int  gfpl_last_step_cut_proof(gfpl_seqbatch* sb, int64_t* counts4);
  * insert (80 doubles each: comparison data, bounds, r = 0 info, the agreement bound as
  * k_cut_search formed it — DESIGN.md §3; layout in k_cut.hip).  Synchronises.      */
 int  gfpl_debug_cut_records(gfpl_seqbatch* sb, int b, double* out, int n_lines);
-/* Every sequence's record of the last step: B x 24 int64 — stage bytes [0..7], the counts of
- * gfpl_last_step_counts [8..15], line-cut steps / exact steps [16..17], inliers after the pose
- * [18], lines without a usable bound [19] (layout: STEP_REC in gfpl_state.hpp).  Synchronises. */
+/* Every sequence's record of the last step: B x GFPL_STEP_REC int64, the slots below (the
+ * gfpl_last_step_* calls are their sums over the batch).  Synchronises.                     */
+enum {
+    /* algorithmic bytes per stage (gfpl_last_step_stage_bytes) and of k_cut_search alone */
+    GFPL_STEP_B_STEREO_POINTS = 0,
+    GFPL_STEP_B_STEREO_LINES = 1,
+    GFPL_STEP_B_CROSS_POINTS = 2,
+    GFPL_STEP_B_CROSS_LINES = 3,
+    GFPL_STEP_B_LINE_CUT = 4,
+    GFPL_STEP_B_POSE = 5,
+    GFPL_STEP_B_TOTAL = 6,
+    GFPL_STEP_B_CUT_SEARCH = 7,
+    /* the counts they are priced on (gfpl_last_step_counts) */
+    GFPL_STEP_N_O = 8,
+    GFPL_STEP_N_K = 9,
+    GFPL_STEP_M_O = 10,
+    GFPL_STEP_S_P = 11,
+    GFPL_STEP_S_L = 12,
+    GFPL_STEP_M_P = 13,
+    GFPL_STEP_M_L = 14,
+    GFPL_STEP_N_INLIERS = 15,
+    /* gfpl_last_step_track_counts */
+    GFPL_STEP_CUT_STEPS = 16,      /* line-cut greedy steps */
+    GFPL_STEP_CUT_EXACT = 17,      /* ... of them evaluated with the reference's arithmetic */
+    GFPL_STEP_INLIERS_POSE = 18,   /* n_inliers after optimize_pose (until it runs: the insert's) */
+    GFPL_STEP_CUT_UNBOUNDED = 19,  /* searched lines without a usable agreement bound */
+    /* proven line cut, cut_proof 1 / 3 (gfpl_last_step_cut_proof); zero in a step without it */
+    GFPL_STEP_PROOF_REDONE = 20,   /* 1: the recorded search was not proven and was redone eagerly */
+    GFPL_STEP_PROOF_STEPS = 21,    /* margined steps proven after the fact */
+    GFPL_STEP_PROOF_VREF = 22,     /* the reference's endpoint variances evaluated for them */
+    GFPL_STEP_PROOF_LINES = 23,    /* lines with margined steps */
+    GFPL_STEP_REC = 24
+};
 int  gfpl_debug_step_records(gfpl_seqbatch* sb, int64_t* out);
 /* B x 8 int64 of diagnostic slots: the clocks instrumented builds of the library write (e.g.
  * -DGFPL_SP_CLOCK: k_stereo_points' phase boundaries); in every build, after a measured-mode step
  * with the 8-sequence-per-wave line-cut search, slots 6 / 7 hold that search wave's HW_ID / XCC_ID
- * (its SIMD and wave slot: the progress exchange's partner check).  Synchronises.               */
+ * (its SIMD and wave slot: the progress exchange's partner check).  Every writer of every build is
+ * listed in csrc/gfpl_records.hpp.  Synchronises.                                                 */
 int  gfpl_debug_clocks(gfpl_seqbatch* sb, int64_t* out);
 /* Per-kernel view of the dominant stages (timing enabled, line cut on):
  * ms4 = device ms of [k_cut_prep, k_cut_search, k_cut_finish, k_pose] of the last

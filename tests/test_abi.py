@@ -39,6 +39,17 @@ def test_library_exports_every_declared_symbol():
     assert set(declared_symbols()) <= exported
 
 
+def test_step_record_slots_match_the_header():
+    """The step record is stated once for C (GFPL_STEP_* in include/gfpl.h) and mirrored once for
+    Python (gfpl.StepSlot): same names, same values, 24 slots."""
+    src = open(os.path.join(ROOT, "include", "gfpl.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    consts = {n: int(v) for n, v in re.findall(r"\bGFPL_STEP_([A-Z0-9_]+)\s*=\s*(\d+)", src)}
+    assert consts.pop("REC") == 24 == gfpl.STEP_REC
+    assert consts == {m.name: int(m) for m in gfpl.StepSlot}
+    assert sorted(consts.values()) == list(range(24))
+
+
 def test_abi_version_and_strerror():
     L = gfpl.hiplib()
     assert L.gfpl_abi_version() == 6   # 6: STEP_REC 24, cut_proof 0-3; 5: gfpl_config.cut_proof; 4: gfpl_detector (image input), event record counts

@@ -16,6 +16,9 @@ from parity import bitwise_equal, compare_core, compare_pose, compare_prev_match
 
 pytestmark = pytest.mark.gpu
 
+S = gfpl.StepSlot
+CUT_SLOTS = [S.CUT_STEPS, S.CUT_EXACT, S.CUT_UNBOUNDED]
+
 
 def test_min_eig_config_accepted():
     ctx = gfpl.Context(K.camera(), gfpl.default_config())
@@ -64,8 +67,8 @@ def _check_line_cut(name, n, rng, got):
         want = _canon(want)
         bad += compare_prev_matched(frames[b], want, st.track, f"s{b} ")
         bad += diff_fields(frames[b], want, K.CUT_FIELDS, what=f"s{b} all rows ")
-        if tuple(rec[b, [16, 17, 19]]) != (n_ref, n_ref, 0):
-            bad.append(f"s{b} steps / exact steps / unbounded lines {rec[b, [16, 17, 19]]} vs {n_ref}")
+        if tuple(rec[b, CUT_SLOTS]) != (n_ref, n_ref, 0):
+            bad.append(f"s{b} steps / exact steps / unbounded lines {rec[b, CUT_SLOTS]} vs {n_ref}")
         steps += n_ref
     assert not bad, "\n".join(bad[:30])
     assert counts["steps"] == steps and counts["exact_steps"] == steps and counts["lines_unbounded"] == 0, counts
@@ -88,7 +91,7 @@ def test_proof_and_certify_modes_ignored(proof, certify):
     for b in range(9):
         for f in K.CUT_FIELDS:
             assert bitwise_equal(got[0][b].arr[f], base[0][b].arr[f]), (b, f)
-    assert (got[1][:, 16:20] == base[1][:, 16:20]).all()
+    assert (got[1][:, S.CUT_STEPS:S.CUT_UNBOUNDED + 1] == base[1][:, S.CUT_STEPS:S.CUT_UNBOUNDED + 1]).all()
 
 
 def test_whole_steps():
@@ -113,8 +116,8 @@ def test_whole_steps():
             bad += compare_track(g.read_last_track(b), want["track"], tag)
             # (the frame the step cut is in the other slot until the next insert)
             bad += compare_prev_matched(g.read_frame(gfpl.CURR, b), want["old"], want["track"], tag + "cut frame ")
-            if rec[b, 16] != want["n"] or rec[b, 17] != want["n"]:
-                bad.append(f"{tag}steps {rec[b, 16:18]} vs {want['n']}")
+            if rec[b, S.CUT_STEPS] != want["n"] or rec[b, S.CUT_EXACT] != want["n"]:
+                bad.append(f"{tag}steps {rec[b, [S.CUT_STEPS, S.CUT_EXACT]]} vs {want['n']}")
             assert len(want["track"]["matched_ls"]) > 10 and want["track"]["n_inliers_ls"] > 5
     g.close()
     ctx.close()

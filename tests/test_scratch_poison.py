@@ -104,5 +104,5 @@ def test_poisoned_scratch_matches_zeroed(monkeypatch, layout):
         parts = sorted({i for b in bad for i in range(3) if d0[k][b][i] != d1[k][b][i]})
         assert not bad, (f"step {k + 1}: state differs for {len(bad)} sequences {bad[:8]} in "
                          f"{[['new frame', 'previous frame (matched rows)', 'track'][i] for i in parts]}")
-    steps = int(sum(r[:, 16].sum() for r in r0))
+    steps = int(sum(r[:, gfpl.StepSlot.CUT_STEPS].sum() for r in r0))
     assert steps > 0   # the line cut ran (greedy steps recorded)

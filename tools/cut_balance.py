@@ -1,19 +1,24 @@
 #!/usr/bin/env python3
 """Line-cut search balance from a bench step-record dump (bench.py --dump-records, a library built
-with -DGFPL_CUT_CLOCK: slot 19 = the k_cut_search wave's duration in 100 MHz wall-clock ticks).
-Per wave (8 consecutive sequences): duration, the groups' greedy steps (slot 16) and matched
-lines (slot 14).  usage: python3 tools/cut_balance.py records.npy"""
+with -DGFPL_CUT_CLOCK: StepSlot.CUT_UNBOUNDED then holds the k_cut_search wave's duration in
+100 MHz wall-clock ticks, STEP_CUT_CLOCK_DURATION in csrc/gfpl_records.hpp).
+Per wave (8 consecutive sequences): duration, the groups' greedy steps and matched lines.
+usage: python3 tools/cut_balance.py records.npy"""
 import json
+import os
 import sys
 
 import numpy as np
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gf-pl-slam_amd"))
+from gfpl import StepSlot as S  # noqa: E402
+
 r = np.load(sys.argv[1])
 B = r.shape[0] // 8 * 8
 w = r[:B].reshape(-1, 8, r.shape[1])
-dur = w[:, 0, 19].astype(np.float64) / 100.0          # us
-steps = w[:, :, 16].astype(np.float64)
-lines = w[:, :, 14].astype(np.float64)
+dur = w[:, 0, S.CUT_UNBOUNDED].astype(np.float64) / 100.0          # us
+steps = w[:, :, S.CUT_STEPS].astype(np.float64)
+lines = w[:, :, S.M_L].astype(np.float64)
 q = lambda a: {k: round(float(v), 2) for k, v in zip(("min", "p10", "p50", "p90", "max", "mean"),
                                                      list(np.percentile(a, [0, 10, 50, 90, 100])) + [a.mean()])}
 out = {"waves": int(w.shape[0]), "wave_us": q(dur), "seq_steps": q(steps.ravel()), "wave_max_steps": q(steps.max(1)),
@@ -24,8 +29,8 @@ out = {"waves": int(w.shape[0]), "wave_us": q(dur), "seq_steps": q(steps.ravel()
        "group_idle_frac": float(1.0 - steps.sum() / (steps.max(1).sum() * 8))}
 print(json.dumps(out))
 
-# the clock build's per-wave start / end / hardware ids (gfpl_debug_clocks, records_clk.npy)
-import os  # noqa: E402
+# the clock build's per-wave start / end / hardware ids (gfpl_debug_clocks, records_clk.npy): debug
+# slots 0-3, DbgCutClock in csrc/gfpl_records.hpp
 ck = sys.argv[1].replace(".npy", "") + "_clk.npy"
 if os.path.exists(ck):
     c = np.load(ck)[:B].reshape(-1, 8, 8)[:, 0, :]

@@ -14,6 +14,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gf-pl-slam_amd"))
 sys.path.insert(0, ROOT)
+# the cut record's slots this tool reads (csrc/gfpl_records.hpp)
+PD_VS, PD_VE, PD_OK, PD_ERR, CUT_NX = 36, 41, 46, 48, 77
 
 
 def main():
@@ -73,17 +75,18 @@ def main():
         cnt = h.last_step_counts()
         print(json.dumps({"frame": k, **tc, "M_l_mean": cnt["M_l"],
                           "exact_frac": tc["exact_steps"] / max(1, tc["steps"])}), flush=True)
-    # records of the cut of the last insert: slot 77-79 = eb (6 floats); PD_VS 36, PD_VE 41
+    # records of the cut of the last insert (csrc/gfpl_records.hpp): CUT_NX = 77 .. 79 = eb (6 floats); PD_VS 36,
+    # PD_VE 41, PD_OK 46, PD_ERR 48
     n = min(a.lines, KL)
     rec = h.debug_cut_records(0, n)
-    eb = rec[:, 77:80].copy().view(np.float32).reshape(n, 6)
+    eb = rec[:, CUT_NX:CUT_NX + 3].copy().view(np.float32).reshape(n, 6)
     for m in range(n):
-        vs0, ve0 = rec[m, 36], rec[m, 41]
+        vs0, ve0 = rec[m, PD_VS], rec[m, PD_VE]
         e = eb[m]
         E0 = (e[1] + e[2] / vs0) / vs0 + (e[3] + e[4] / ve0) / ve0 if vs0 > 0 and ve0 > 0 else float("nan")
         print(json.dumps({"line": m, "R0": float(e[0]), "A1": float(e[1]), "A2": float(e[2]), "B1": float(e[3]),
                           "B2": float(e[4]), "EV": float(e[5]), "vs0": vs0, "ve0": ve0, "E_at_0": E0,
-                          "pd_ok": rec[m, 46], "err_floats": rec[m, 48:55].copy().view(np.float32).tolist()}))
+                          "pd_ok": rec[m, PD_OK], "err_floats": rec[m, PD_ERR:PD_ERR + 7].copy().view(np.float32).tolist()}))
     h.close()
     ctx.close()
 

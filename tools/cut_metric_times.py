@@ -9,7 +9,8 @@ same frames for every configuration in one process:
   logdet         the default (margined search), for scale
 Times are gfpl_get_kernel_times (HIP events around k_cut_prep / the search / k_cut_finish) of each
 step after the first; for min_eig also the search's counters: steps, metric evaluations and Jacobi
-sweeps that rotated (gfpl_debug_clocks slots 1 / 0).  U unique sequences are generated and tiled to B.
+sweeps that rotated (gfpl_debug_clocks slots 1 / 0: DbgCutEig in csrc/gfpl_records.hpp).  U unique sequences are
+generated and tiled to B.
 
 usage: python3 tools/cut_metric_times.py [--batch 16384] [--unique 1024] [--frames 4]
 prints one JSON line per configuration.

@@ -3,7 +3,7 @@
 built by `tools/build_variant.sh DIR -DGFPL_CUT_PCLOCK`): per search wave, shader-clock cycles in
 the step evaluation + decision, exact rounds, bookkeeping and line transitions (slots 0-3), the
 transitions' phases (slots 4-6), and the loop iterations / transitions counted (slot 7: n_it << 32 |
-n_tr; the 8 sequences of a wave carry the wave's).
+n_tr; the 8 sequences of a wave carry the wave's) — DbgCutPhase in csrc/gfpl_records.hpp.
 
 usage: python3 tools/cut_phases.py X_clk.npy [group size, default 8]
 """

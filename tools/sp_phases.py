@@ -3,7 +3,8 @@
 built with -DGFPL_SP_CLOCK): per workgroup (sequence) the 100 MHz wall clock at the kernel start,
 after the setup (counting sorts), the band scan, the SAD-job tile sort, the sub-pixel SAD and the
 end (emission sort, stores).  With --lines (a -DGFPL_SL_CLOCK build): k_stereo_lines' train-row staging,
-knn pass, medians, triangulation + emission.  usage: python3 tools/sp_phases.py records_clk.npy [--lines]"""
+knn pass, medians, triangulation + emission.  (Debug slots 0-5 / 0-4: the GFPL_SP_CLOCK / GFPL_SL_CLOCK
+rows of the table in csrc/gfpl_records.hpp.)  usage: python3 tools/sp_phases.py records_clk.npy [--lines]"""
 import json
 import sys
 

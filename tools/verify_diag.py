@@ -28,6 +28,7 @@ def main():
     masks, worst, terms, xchk = [], [], [], []
     for k in range(1, F):
         h.insertStereoPair(D.frames(k))
+        # k_cut_verify's slots: DbgVerify in csrc/gfpl_records.hpp (terms 0-3, mask 4, worst 5, xchk 6)
         d = h.debug_clocks()
         masks.append(d[:, 4].copy())
         worst.append(d[:, 5].copy().view(np.float64))
