@@ -1096,6 +1096,98 @@ int gfpl_kf_local_map_matches(gfpl_ctx* c, const gfpl_map_view* m, const gfpl_kf
     return GFPL_OK;
 }
 
+void gfpl_default_loop_params(gfpl_loop_params* p) {
+    if (!p) return;
+    p->lc_res = 1.5;    // src/config.cpp:62-66
+    p->lc_unc = 0.01;
+    p->lc_inl = 0.3;
+    p->lc_trs = 1.5;
+    p->lc_rot = 35.0;
+}
+
+// MapHandler::isLoopClosure + computeRelativePoseGN (src/mapHandler.cpp:3078-3545) over n candidate
+// pairs: per pair and kind two knn-2 launches (k_knn2m), then ONE k_loop_closure launch (k_loop.hip)
+// with a workgroup per pair; keyframe rate, so the scratch is allocated per call.
+int gfpl_kf_loop_closure(gfpl_ctx* c, const gfpl_kf_view* kf0, const gfpl_kf_view* kf1, int n,
+                         const gfpl_loop_params* prm, int pt_cap, int ls_cap, int32_t* pt_pairs, uint8_t* pt_inlier,
+                         int32_t* ls_pairs, uint8_t* ls_inlier, gfpl_loop_result* out) {
+    if (!c || !prm || n < 0 || pt_cap < 0 || ls_cap < 0 || !c->has_cam) return GFPL_E_INVALID;
+    if (n == 0) return GFPL_OK;
+    if (!kf0 || !kf1 || !out) return GFPL_E_INVALID;
+    size_t n_idx = 0;   // knn-2 rows over all pairs, kinds and directions
+    bool any_pt = false, any_ls = false;
+    for (int i = 0; i < n; ++i) {
+        const gfpl_kf_view &a = kf0[i], &b = kf1[i];
+        if (a.n_pt < 0 || b.n_pt < 0 || a.n_ls < 0 || b.n_ls < 0) return GFPL_E_INVALID;
+        if (a.n_pt >= 2 && (!a.pdesc || !a.P)) return GFPL_E_INVALID;
+        if (b.n_pt >= 2 && (!b.pdesc || !b.pl)) return GFPL_E_INVALID;
+        if (a.n_ls >= 2 && (!a.ldesc || !a.sP || !a.eP)) return GFPL_E_INVALID;
+        if (b.n_ls >= 2 && (!b.ldesc || !b.le)) return GFPL_E_INVALID;
+        if (a.n_pt >= 2 && b.n_pt >= 2) { any_pt = true; n_idx += (size_t)a.n_pt + b.n_pt; }   // ledger U4
+        if (a.n_ls >= 2 && b.n_ls >= 2) { any_ls = true; n_idx += (size_t)a.n_ls + b.n_ls; }
+    }
+    if (any_pt && (!pt_pairs || !pt_inlier)) return GFPL_E_INVALID;
+    if (any_ls && (!ls_pairs || !ls_inlier)) return GFPL_E_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (kf0[i].n_pt > pt_cap || kf0[i].n_ls > ls_cap) return GFPL_E_CAPACITY;
+    HIPCHK(hipSetDevice(c->device));
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t b_pairs = up16((size_t)n * sizeof(gfpl::LoopPair)), b_res = up16((size_t)n * sizeof(gfpl_loop_result));
+    const size_t b_idx = up16(2 * n_idx * sizeof(int32_t)), b_dist = up16(2 * n_idx * sizeof(float));
+    char* scr = nullptr;
+    HIPCHK(hipMalloc(&scr, b_pairs + b_res + b_idx + b_dist + 64));
+    gfpl::LoopPair* d_pairs = reinterpret_cast<gfpl::LoopPair*>(scr);
+    gfpl_loop_result* d_res = reinterpret_cast<gfpl_loop_result*>(scr + b_pairs);
+    int32_t* idx = reinterpret_cast<int32_t*>(scr + b_pairs + b_res);
+    float* dist = reinterpret_cast<float*>(scr + b_pairs + b_res + b_idx);
+    std::vector<gfpl::LoopPair> hp((size_t)n);
+    hipError_t e = hipSuccess;
+    size_t o = 0;
+    for (int i = 0; i < n && e == hipSuccess; ++i) {
+        const gfpl_kf_view &a = kf0[i], &b = kf1[i];
+        gfpl::LoopPair& p = hp[i];
+        std::memset(&p, 0, sizeof p);
+        p.n0_pt = a.n_pt; p.n0_ls = a.n_ls;
+        p.P0 = a.P; p.pl1 = b.pl; p.sP0 = a.sP; p.eP0 = a.eP; p.le1 = b.le;
+        for (int kind = 0; kind < 2 && e == hipSuccess; ++kind) {
+            const int n0 = kind == 0 ? a.n_pt : a.n_ls, n1 = kind == 0 ? b.n_pt : b.n_ls;
+            if (n0 < 2 || n1 < 2) continue;
+            const uint8_t* d0 = kind == 0 ? a.pdesc : a.ldesc;
+            const uint8_t* d1 = kind == 0 ? b.pdesc : b.ldesc;
+            int32_t* i12 = idx + 2 * o;
+            float* f12 = dist + 2 * o;
+            int32_t* i21 = i12 + 2 * (size_t)n0;
+            float* f21 = f12 + 2 * (size_t)n0;
+            o += (size_t)n0 + n1;
+            e = launch_knn2(d0, n0, d1, n1, 1, i12, f12, c->stream);   // NORM_HAMMING (:3106 / :3173)
+            if (e == hipSuccess) e = launch_knn2(d1, n1, d0, n0, 1, i21, f21, c->stream);
+            if (kind == 0) { p.pi12 = i12; p.pi21 = i21; } else { p.li12 = i12; p.li21 = i21; }
+        }
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_pairs, hp.data(), (size_t)n * sizeof(gfpl::LoopPair), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        gfpl::LoopArgs la;
+        std::memset(&la, 0, sizeof la);
+        la.cam = devcam(c->cam);
+        la.homog_th = c->cfg.homog_th;
+        la.max_iters = c->cfg.max_iters;
+        la.prm = *prm;
+        la.pairs = d_pairs;
+        la.pt_cap = pt_cap; la.ls_cap = ls_cap;
+        la.pt_pairs = pt_pairs; la.pt_inlier = pt_inlier;
+        la.ls_pairs = ls_pairs; la.ls_inlier = ls_inlier;
+        la.out = d_res;
+        e = launch_loop_closure(la, n, c->stream);
+    }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(out, d_res, (size_t)n * sizeof(gfpl_loop_result), hipMemcpyDeviceToHost, c->stream);
+    hipError_t es = hipStreamSynchronize(c->stream);   // also on an error path: hp and scr are still in use
+    hipError_t ef = hipFree(scr);
+    if (e != hipSuccess || es != hipSuccess || ef != hipSuccess) return GFPL_E_HIP;
+    return GFPL_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------ transfer --

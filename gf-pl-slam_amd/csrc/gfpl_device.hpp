@@ -189,6 +189,52 @@ GFPL_DEV double det_cos(double x) {
     }
 }
 
+// e_acos.c — pin N6 (same notice as above): + - * / and sqrt only, so the bits follow from N1
+GFPL_DEV double det_acos(double x) {
+    const double pi = 3.14159265358979311600e+00, pio2_hi = 1.57079632679489655800e+00,
+                 pio2_lo = 6.12323399573676603587e-17,
+                 pS0 = 1.66666666666666657415e-01, pS1 = -3.25565818622400915405e-01,
+                 pS2 = 2.01212532134862925881e-01, pS3 = -4.00555345006794114027e-02,
+                 pS4 = 7.91534994289814532176e-04, pS5 = 3.47933107596021167570e-05,
+                 qS1 = -2.40339491173441421878e+00, qS2 = 2.02094576023350569471e+00,
+                 qS3 = -6.88283971605453293030e-01, qS4 = 7.70381505559019352791e-02;
+    const int32_t hx = (int32_t)hiw(x);
+    const int32_t ix = hx & 0x7fffffff;
+    if (ix >= 0x3ff00000) {
+        if ((((uint32_t)ix - 0x3ff00000u) | low(x)) == 0) {
+            if (hx > 0) return 0.0;
+            return pi + 2.0 * pio2_lo;
+        }
+        return (x - x) / (x - x);
+    }
+    if (ix < 0x3fe00000) {
+        if (ix <= 0x3c600000) return pio2_hi + pio2_lo;
+        const double z = x * x;
+        const double p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+        const double q = 1.0 + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+        const double r = p / q;
+        return pio2_hi - (x - (pio2_lo - r * x));
+    }
+    if (hx < 0) {
+        const double z = (1.0 + x) * 0.5;
+        const double p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+        const double q = 1.0 + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+        const double s = sqrt(z);
+        const double r = p / q;
+        const double w = r * s - pio2_lo;
+        return pi - 2.0 * (s + w);
+    }
+    const double z = (1.0 - x) * 0.5;
+    const double s = sqrt(z);
+    const double df = from_words(hiw(s), 0);
+    const double c = (z - df * df) / (s + df);
+    const double p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+    const double q = 1.0 + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+    const double r = p / q;
+    const double w = r * s + c;
+    return 2.0 * (df + w);
+}
+
 GFPL_DEV double ref_max(double a, double b) { return (a < b) ? b : a; }
 
 // ------------------------------------------------------------- Hamming
@@ -385,6 +431,63 @@ GFPL_DEV void expmap_se3(const double* x, double* T) {
     T[4] = R[3]; T[5] = R[4]; T[6] = R[5]; T[7] = t[1];
     T[8] = R[6]; T[9] = R[7]; T[10] = R[8]; T[11] = t[2];
     T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
+}
+
+// Matrix3d::inverse(), Eigen 3.3's size-3 path (cofactors, det along column 0) — pin N7
+GFPL_DEV void inverse3(const double* m, double* out) {
+    double c[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+            c[i * 3 + j] = m[i1 * 3 + j1] * m[i2 * 3 + j2] - m[i1 * 3 + j2] * m[i2 * 3 + j1];
+        }
+    const double det = (c[0] * m[0] + c[3] * m[3]) + c[6] * m[6];
+    const double invdet = 1.0 / det;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[r * 3 + k] = c[k * 3 + r] * invdet;
+}
+
+// logmap_se3 (src/auxiliar.cpp:184-214) as written — pin N8 (cosine = -1 divides by sine = 0)
+GFPL_DEV void logmap_se3(const double* T, double* x) {
+    double R[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) R[i * 3 + j] = T[i * 4 + j];
+    const double Vt[3] = {T[3], T[7], T[11]};
+    double w[3] = {0.0, 0.0, 0.0};
+    double V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    double cosine = (((R[0] + R[4]) + R[8]) - 1.0) / 2.0;
+    if (cosine > 1.0) cosine = 1.0;
+    else if (cosine < -1.0) cosine = -1.0;
+    double sine = sqrt(1.0 - cosine * cosine);
+    if (sine > 1.0) sine = 1.0;
+    else if (sine < -1.0) sine = -1.0;
+    const double theta = det_acos(cosine);
+    if (theta > 0.000001) {
+        const double two_sine = 2.0 * sine;
+        w[0] = (theta * (R[7] - R[5])) / two_sine;
+        w[1] = (theta * (R[2] - R[6])) / two_sine;
+        w[2] = (theta * (R[3] - R[1])) / two_sine;
+        double s[9], ss[9];
+        skew3(w, s);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) s[i] = s[i] / theta;
+        mat3_mul(s, s, ss);
+        const double omc = 1.0 - cosine, tms = theta - sine;
+        const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+#pragma unroll
+        for (int i = 0; i < 9; ++i) V[i] = (I[i] + (s[i] * omc) / theta) + (ss[i] * tms) / theta;
+    }
+    double Vi[9];
+    inverse3(V, Vi);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) x[i] = (Vi[i * 3 + 0] * Vt[0] + Vi[i * 3 + 1] * Vt[1]) + Vi[i * 3 + 2] * Vt[2];
+    x[3] = w[0]; x[4] = w[1]; x[5] = w[2];
 }
 
 // logdet (include/linespec.h:43-56) on a 6x6 given by its lower triangle

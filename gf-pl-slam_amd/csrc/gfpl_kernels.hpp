@@ -89,6 +89,33 @@ hipError_t launch_kf_gate(const KfGate& g, hipStream_t s);
 hipError_t launch_kf_map_filter(const DevCam& cam, const double* T1, const double* P, int n, int lines,
                                 int32_t* loc, uint8_t* desc_out, const uint8_t* desc_in, int* count, hipStream_t s);
 
+
+// isLoopClosure (k_loop.hip): one candidate pair's knn-2 lists and feature arrays; all pointers device.
+// pi12 / li12 are null for a kind with fewer than two rows on either keyframe (ledger U4).
+struct LoopPair {
+    int n0_pt, n0_ls;
+    const int32_t *pi12, *pi21;   // point knn-2 kf0 -> kf1 [2 n0_pt], kf1 -> kf0 [2 n1_pt]
+    const int32_t *li12, *li21;   // the same for lines
+    const double* P0;             // kf0 P [n0_pt][3]
+    const double* pl1;            // kf1 pl [n1_pt][2]
+    const double *sP0, *eP0;      // kf0 sP / eP [n0_ls][3]
+    const double* le1;            // kf1 le [n1_ls][3]
+};
+struct LoopArgs {
+    DevCam cam;
+    double homog_th;
+    int max_iters;
+    gfpl_loop_params prm;
+    const LoopPair* pairs;        // [n]
+    int pt_cap, ls_cap;
+    int32_t* pt_pairs;            // [n][pt_cap][2]
+    uint8_t* pt_inlier;           // [n][pt_cap]
+    int32_t* ls_pairs;
+    uint8_t* ls_inlier;
+    gfpl_loop_result* out;        // [n]
+};
+hipError_t launch_loop_closure(const LoopArgs& a, int n, hipStream_t s);
+
 }  // namespace gfpl
 
 namespace gfpl {

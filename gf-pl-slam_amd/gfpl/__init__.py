@@ -212,6 +212,31 @@ class KeyFrameView:
             setattr(self.s, cf, _ptr(a))
 
 
+class LoopParams(C.Structure):
+    """gfpl_loop_params: Config::lcRes / lcUnc / lcInl / lcTrs / lcRot (src/config.cpp:62-66);
+    LoopParams.default() fills the reference's values."""
+    _fields_ = [("lc_res", C.c_double), ("lc_unc", C.c_double), ("lc_inl", C.c_double),
+                ("lc_trs", C.c_double), ("lc_rot", C.c_double)]
+
+    @classmethod
+    def default(cls, **over) -> "LoopParams":
+        p = cls()
+        hiplib().gfpl_default_loop_params(C.byref(p))
+        for k, v in over.items():
+            setattr(p, k, v)
+        return p
+
+
+class LoopResult(C.Structure):
+    """gfpl_loop_result: MapHandler::isLoopClosure's decision for one candidate pair; gates bit 0 res,
+    1 unc, 2 inl, 3 trs, 4 rot; pose_inc is valid when is_lc."""
+    _fields_ = [("is_lc", C.c_int32), ("gates", C.c_int32), ("n_pt", C.c_int32), ("n_ls", C.c_int32),
+                ("n_pt_inl", C.c_int32), ("n_ls_inl", C.c_int32), ("iters", C.c_int32), ("pad", C.c_int32),
+                ("e", C.c_double), ("unc", C.c_double), ("ratio_inliers", C.c_double), ("trs", C.c_double),
+                ("rot", C.c_double), ("x_inc", C.c_double * 6), ("pose_inc", C.c_double * 6),
+                ("T_inc", C.c_double * 16)]
+
+
 class MapViewStruct(C.Structure):
     """gfpl_map_view: the local map rows lookForCommonMatches' second stage reads."""
     _fields_ = [("n_pt", C.c_int), ("pdesc", _vp), ("P", _vp), ("n_ls", C.c_int), ("ldesc", _vp), ("L", _vp)]
@@ -392,6 +417,8 @@ def hiplib() -> C.CDLL:
             "gfpl_knn2_hamming": ([P, P, C.c_int, P, C.c_int, C.c_int, P, P], C.c_int),
             "gfpl_kf_common_matches": ([P, P, P, P, P, P, P], C.c_int),
             "gfpl_kf_local_map_matches": ([P, P, P, C.c_double, C.c_double, P, P, P, P], C.c_int),
+            "gfpl_default_loop_params": ([P], None),
+            "gfpl_kf_loop_closure": ([P, P, P, C.c_int, P, C.c_int, C.c_int, P, P, P, P, P], C.c_int),
             "gfpl_read_frame": ([P, C.c_int, C.c_int, P], C.c_int),
             "gfpl_write_frame": ([P, C.c_int, C.c_int, P], C.c_int),
             "gfpl_read_track": ([P, C.c_int, P], C.c_int),
@@ -880,6 +907,38 @@ class Context:
                                                _ptr(lp), C.byref(nls)), "kf_local_map_matches")
         return (pp[: 2 * npt.value].cpu().numpy().reshape(-1, 2),
                 lp[: 2 * nls.value].cpu().numpy().reshape(-1, 2))
+
+    def isLoopClosure(self, kf0_views, kf1_views, params: Optional[LoopParams] = None):
+        """MapHandler::isLoopClosure (src/mapHandler.cpp:3078-3545) for a batch of candidate pairs
+        (kf0_views[i], kf1_views[i]) in one call: per pair (LoopResult, pt_pairs [n_pt][2], pt_inlier
+        [n_pt] u8, ls_pairs [n_ls][2], ls_inlier [n_ls]); the pairs are (kf0 row, kf1 row) in kf0 row
+        order.  A single KeyFrameView pair may be passed instead of two lists."""
+        import torch
+        if isinstance(kf0_views, KeyFrameView):
+            kf0_views, kf1_views = [kf0_views], [kf1_views]
+        n = len(kf0_views)
+        if len(kf1_views) != n:
+            raise GfplError(-1, "isLoopClosure: kf0_views and kf1_views differ in length")
+        prm = params if params is not None else LoopParams.default()
+        v0 = (KFViewStruct * max(n, 1))(*[k.s for k in kf0_views])
+        v1 = (KFViewStruct * max(n, 1))(*[k.s for k in kf1_views])
+        pt_cap = max([k.s.n_pt for k in kf0_views] + [1])
+        ls_cap = max([k.s.n_ls for k in kf0_views] + [1])
+        dev = torch.device("cuda", torch.cuda.current_device())
+        pp = torch.zeros((max(n, 1), pt_cap, 2), dtype=torch.int32, device=dev)
+        pi = torch.zeros((max(n, 1), pt_cap), dtype=torch.uint8, device=dev)
+        lp = torch.zeros((max(n, 1), ls_cap, 2), dtype=torch.int32, device=dev)
+        li = torch.zeros((max(n, 1), ls_cap), dtype=torch.uint8, device=dev)
+        out = (LoopResult * max(n, 1))()
+        torch.cuda.synchronize()
+        check(self.L.gfpl_kf_loop_closure(self.h, v0, v1, n, C.byref(prm), pt_cap, ls_cap, _ptr(pp), _ptr(pi),
+                                          _ptr(lp), _ptr(li), out), "kf_loop_closure")
+        pp, pi, lp, li = pp.cpu().numpy(), pi.cpu().numpy(), lp.cpu().numpy(), li.cpu().numpy()
+        res = []
+        for i in range(n):
+            r = LoopResult.from_buffer_copy(out[i])
+            res.append((r, pp[i, :r.n_pt].copy(), pi[i, :r.n_pt].copy(), lp[i, :r.n_ls].copy(), li[i, :r.n_ls].copy()))
+        return res
 
     def close(self):
         """gfpl_destroy.  Refused (GfplError, the handle kept) while a StereoFrameHandler

@@ -691,6 +691,41 @@ int  gfpl_kf_local_map_matches(gfpl_ctx* ctx, const gfpl_map_view* map, const gf
                                double max_kf_epip_p, double max_kf_epip_l,
                                int32_t* pt_pairs, int* n_pt_pairs, int32_t* ls_pairs, int* n_ls_pairs);
 
+/* MapHandler::isLoopClosure with its solver computeRelativePoseGN (src/mapHandler.cpp:
+ * 3078-3545), batched over n candidate keyframe pairs (one workgroup each).  Per pair and
+ * feature kind: knn-2 NORM_HAMMING both ways, row i of kf0 kept when it is the best match of
+ * its best match (no ratio and no MAD test), pairs in kf0 row order; the features take the
+ * class-default sigma2 = 1.0 and inlier = true; Config::maxIters Gauss-Newton iterations from
+ * T_inc = I over the point and line residuals of kf0's 3D under T_inc against kf1's
+ * observations; the chi-square outlier pass (sqrt(7.815)); the five gates below.  The DBoW2
+ * candidate search and the pose graph stay with the caller.  T_kf_w, pt_sigma2 and ls_sigma2
+ * of the views are not read.  A kind with fewer than two rows on either keyframe yields no
+ * pairs (ledger U4).                                                                       */
+typedef struct gfpl_loop_params { double lc_res, lc_unc, lc_inl, lc_trs, lc_rot; } gfpl_loop_params;
+/* Config::lcRes / lcUnc / lcInl / lcTrs / lcRot: 1.5, 0.01, 0.3, 1.5, 35.0 (src/config.cpp:62-66) */
+void gfpl_default_loop_params(gfpl_loop_params* prm);
+typedef struct gfpl_loop_result {
+    int32_t is_lc, gates;            /* gates: bit 0 res, 1 unc, 2 inl, 3 trs, 4 rot (31 = all hold) */
+    int32_t n_pt, n_ls;              /* mutual-best pairs (common_pt / common_ls)                    */
+    int32_t n_pt_inl, n_ls_inl;      /* of them inliers after the outlier pass                       */
+    int32_t iters, pad;              /* GN iterations whose sums were evaluated                      */
+    double  e, unc, ratio_inliers, trs, rot;   /* the five gated values (rot in degrees)             */
+    double  x_inc[6];                /* logmap_se3(T_inc)                                            */
+    double  pose_inc[6];             /* logmap_se3(inverse_se3(T_inc)) when is_lc, else 0            */
+    double  T_inc[16];
+} gfpl_loop_result;
+/* kf0 / kf1: HOST arrays of n views whose pointers are DEVICE memory.  pt_pairs [n][pt_cap][2],
+ * pt_inlier [n][pt_cap], ls_pairs [n][ls_cap][2], ls_inlier [n][ls_cap] (device): pair i's first
+ * out[i].n_pt / n_ls rows are its (kf0 row, kf1 row) pairs and their inlier flags.  out: host [n].
+ * max_iters, homog_th and the camera are the context's.  GFPL_E_INVALID for a NULL pointer, n < 0,
+ * a context without a camera, or a view with >= 2 rows of a kind whose arrays of that kind are
+ * NULL; GFPL_E_CAPACITY (nothing launched) when some kf0[i].n_pt > pt_cap or n_ls > ls_cap;
+ * n = 0 is GFPL_OK.  Synchronises.                                                          */
+int  gfpl_kf_loop_closure(gfpl_ctx* ctx, const gfpl_kf_view* kf0, const gfpl_kf_view* kf1, int n,
+                          const gfpl_loop_params* prm, int pt_cap, int ls_cap,
+                          int32_t* pt_pairs, uint8_t* pt_inlier, int32_t* ls_pairs, uint8_t* ls_inlier,
+                          gfpl_loop_result* out);
+
 /* ----------------------------------------------------- state transfer ----- */
 /* Copy one sequence's frame state device -> host (synchronises).            */
 int  gfpl_read_frame(gfpl_seqbatch* sb, int which, int seq, gfpl_frame_host* out);
