@@ -116,6 +116,28 @@ struct LoopArgs {
 };
 hipError_t launch_loop_closure(const LoopArgs& a, int n, hipStream_t s);
 
+// DBoW2 transform and score (k_bow.hip); all pointers device.  The vocabulary's arrays are BowVocabMem's.
+struct BowVocabDev {
+    const uint8_t* desc;
+    const BowNode* node;
+    const int32_t* rank_word;
+    const double* rank_weight;
+    int weighting;                // GFPL_BOW_TF_IDF ... GFPL_BOW_BINARY
+};
+struct BowSet {                   // one descriptor set of a transform call
+    const uint8_t* desc;          // [count][32]
+    int count, pad;
+};
+struct BowPair {                  // one pair of a score call: L1Scoring::score(a, b)
+    const int32_t* ia; const double* va;
+    const int32_t* ib; const double* vb;
+    int na, nb;
+};
+// keys [n][cap]: scratch; word_ids / values [n][cap], n_words [n]: outputs; max_count: the largest count
+hipError_t launch_bow_transform(const BowVocabDev& v, const BowSet* sets, int n, int max_count, int cap, int32_t* keys,
+                                int32_t* word_ids, double* values, int32_t* n_words, hipStream_t s);
+hipError_t launch_bow_score(const BowPair* pairs, int n, double* scores, hipStream_t s);
+
 }  // namespace gfpl
 
 namespace gfpl {

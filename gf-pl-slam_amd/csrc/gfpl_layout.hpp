@@ -215,4 +215,41 @@ struct LsdGrowLds {
     GFPL_HD LsdGrowLds(unsigned char* smem, int cid_cap) : c(smem), cid_cap(cid_cap) {}
 };
 
+// ---- the device copy of a DBoW2 vocabulary (gfpl_vocab, k_bow.hip).  Nodes are renumbered breadth
+// first from the root (device node 0), so a node's children are consecutive device nodes in
+// Node::children order and a child's 32-byte descriptor row and its record sit at child0 + position.
+// Leaves are ranked by ascending word id: the kernels sort ranks (the same order as word ids) and
+// look the word id and the weight up by rank.
+constexpr int BOW_MAX_CHILDREN = 32;        // two child positions per lane of a 16-lane row (k_bow_descend)
+constexpr int BOW_STOP = 0x7fffffff;        // key of a feature whose leaf weight is not > 0 (sorts last)
+struct BowNode {
+    int32_t child0;    // device node of the first child
+    int32_t n_child;   // 0: a leaf
+    int32_t key;       // leaf: its rank, or BOW_STOP when !(weight > 0); inner node: unused
+    int32_t pad;
+};
+struct BowVocabMem {
+    Carver c;
+    int n_nodes, n_leaves;
+    uint8_t* desc = c.take<uint8_t>((size_t)n_nodes * 32);      // [n_nodes][32], rows 32-B aligned
+    BowNode* node = c.take<BowNode>((size_t)n_nodes);
+    int32_t* rank_word = c.take<int32_t>((size_t)n_leaves);     // word id of rank r, ascending
+    double* rank_weight = c.take<double>((size_t)n_leaves);
+    size_t bytes = c.off;
+    BowVocabMem(char* base, int n_nodes, int n_leaves) : c{0, base}, n_nodes(n_nodes), n_leaves(n_leaves) {}
+};
+
+// ---- k_bow_finish: one set's keys (padded to a power of two p2 for the bitonic sort), the
+// unnormalised values of its words, the block scan's wave sums and the norm
+struct BowFinishLds {
+    LdsCarver c;
+    int p2, max_count;
+    int32_t* keys = c.take<int32_t>(p2);
+    double* vals = c.take<double>(max_count, 8);
+    double* norm = c.take<double>(1);
+    int* scan = c.take<int>(8);
+    int bytes = c.off;
+    GFPL_HD BowFinishLds(unsigned char* smem, int p2, int max_count) : c(smem), p2(p2), max_count(max_count) {}
+};
+
 }  // namespace gfpl

@@ -36,6 +36,7 @@ GFPL_DEV int wave_sum(int v) {
 #define DPP_XOR1 0xB1
 #define DPP_XOR2 0x4E
 #define DPP_HALF_MIRROR 0x141
+#define DPP_ROW_MIRROR 0x140   // lane i <-> 15 - i of a 16-lane row: the fourth step, for groups of 16
 template <int CTRL>
 GFPL_DEV int dpp_i32(int v) {
     return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false);

@@ -237,6 +237,49 @@ class LoopResult(C.Structure):
                 ("T_inc", C.c_double * 16)]
 
 
+# DBoW2::WeightingType and the keyframe database's modes (include/gfpl.h)
+BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
+BOW_L1_NORM = 0
+BOW_MODE_P, BOW_MODE_L, BOW_MODE_PL = 0, 1, 2
+
+
+class VocabDesc(C.Structure):
+    """gfpl_vocab_desc: a DBoW2 vocabulary tree as flat host arrays."""
+    _fields_ = [("n_nodes", C.c_int), ("child_off", _vp), ("child", _vp), ("desc", _vp), ("weight", _vp),
+                ("word_id", _vp), ("weighting", C.c_int), ("scoring", C.c_int)]
+
+
+class BowVec(C.Structure):
+    """gfpl_bow_vec: a BowVector on the device, count entries in ascending word id."""
+    _fields_ = [("ids", _vp), ("values", _vp), ("count", C.c_int)]
+
+
+class BowStats(C.Structure):
+    """gfpl_bow_stats: what insertKFBowVectorPL weighs the two scores with (src/mapHandler.cpp:2940-2972)."""
+    _fields_ = [("n_pt", C.c_int32), ("n_ls", C.c_int32), ("std_pt", C.c_double), ("std_ls", C.c_double)]
+
+
+class LcSearchParams(C.Structure):
+    """gfpl_lc_search_params: Config::lcKFDist / lcKFMaxDist / lcNKFClosest / minLMCovGraph / minKFLocalMap;
+    LcSearchParams.default() fills the reference's values (100, 20, 4, 30, 3)."""
+    _fields_ = [("lc_kf_dist", C.c_int32), ("lc_kf_max_dist", C.c_int32), ("lc_nkf_closest", C.c_int32),
+                ("min_lm_cov_graph", C.c_int32), ("min_kf_local_map", C.c_int32)]
+
+    @classmethod
+    def default(cls, **over) -> "LcSearchParams":
+        p = cls()
+        hiplib().gfpl_default_lc_search_params(C.byref(p))
+        for k, v in over.items():
+            setattr(p, k, v)
+        return p
+
+
+class LcSearchInfo(C.Structure):
+    """gfpl_lc_search_info: lookForLoopCandidates' intermediate values (what the reference prints)."""
+    _fields_ = [("lc_min_score", C.c_double), ("nkf_closest", C.c_int32), ("idx_max", C.c_int32),
+                ("n_list", C.c_int32), ("pad", C.c_int32)]
+
+
 class MapViewStruct(C.Structure):
     """gfpl_map_view: the local map rows lookForCommonMatches' second stage reads."""
     _fields_ = [("n_pt", C.c_int), ("pdesc", _vp), ("P", _vp), ("n_ls", C.c_int), ("ldesc", _vp), ("L", _vp)]
@@ -419,6 +462,19 @@ def hiplib() -> C.CDLL:
             "gfpl_kf_local_map_matches": ([P, P, P, C.c_double, C.c_double, P, P, P, P], C.c_int),
             "gfpl_default_loop_params": ([P], None),
             "gfpl_kf_loop_closure": ([P, P, P, C.c_int, P, C.c_int, C.c_int, P, P, P, P, P], C.c_int),
+            "gfpl_vocab_create": ([P, P, P], C.c_int),
+            "gfpl_vocab_destroy": ([P], C.c_int),
+            "gfpl_vocab_check": ([P], C.c_int),
+            "gfpl_bow_transform": ([P, P, C.c_int, P, P, C.c_int, P, P, P], C.c_int),
+            "gfpl_bow_score": ([P, P, P, C.c_int, P], C.c_int),
+            "gfpl_kf_bow_stats": ([P, C.c_int, P, P, C.c_int, P], C.c_int),
+            "gfpl_bowdb_create": ([P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P], C.c_int),
+            "gfpl_bowdb_destroy": ([P], C.c_int),
+            "gfpl_bowdb_insert": ([P, C.c_int, P, P, P], C.c_int),
+            "gfpl_bowdb_erase": ([P, C.c_int], C.c_int),
+            "gfpl_bowdb_vector": ([P, C.c_int, C.c_int, P, P, P], C.c_int),
+            "gfpl_default_lc_search_params": ([P], None),
+            "gfpl_kf_loop_candidates": ([P, P, P, C.c_int, P, P, P], C.c_int),
             "gfpl_read_frame": ([P, C.c_int, C.c_int, P], C.c_int),
             "gfpl_write_frame": ([P, C.c_int, C.c_int, P], C.c_int),
             "gfpl_read_track": ([P, C.c_int, P], C.c_int),
@@ -939,6 +995,54 @@ class Context:
             r = LoopResult.from_buffer_copy(out[i])
             res.append((r, pp[i, :r.n_pt].copy(), pi[i, :r.n_pt].copy(), lp[i, :r.n_ls].copy(), li[i, :r.n_ls].copy()))
         return res
+
+    def bowTransform(self, voc: "Vocabulary", desc_sets, cap: Optional[int] = None):
+        """TemplatedVocabulary::transform(features, BowVector&) for a batch of descriptor sets (device u8
+        tensors [count][32], e.g. a keyframe's pdesc_l or ldesc_l) in one call: per set (word ids int32,
+        values f64), in ascending word id.  cap: the rows of the output arrays (default: the largest
+        count)."""
+        import torch
+        n = len(desc_sets)
+        counts = [int(d.shape[0]) for d in desc_sets]
+        if cap is None:
+            cap = max(counts + [1])
+        dev = torch.device("cuda", self.device)
+        ptrs = (C.c_void_p * max(n, 1))(*[_ptr(d) if c else None for d, c in zip(desc_sets, counts)])
+        cnt = (C.c_int * max(n, 1))(*counts)
+        ids = torch.zeros((max(n, 1), max(cap, 1)), dtype=torch.int32, device=dev)
+        vals = torch.zeros((max(n, 1), max(cap, 1)), dtype=torch.float64, device=dev)
+        nw = (C.c_int * max(n, 1))()
+        torch.cuda.synchronize()
+        check(self.L.gfpl_bow_transform(self.h, voc.h, n, ptrs, cnt, cap, _ptr(ids), _ptr(vals), nw), "bow_transform")
+        ids, vals = ids.cpu().numpy(), vals.cpu().numpy()
+        return [(ids[i, :nw[i]].copy(), vals[i, :nw[i]].copy()) for i in range(n)]
+
+    def bowScore(self, a, b) -> np.ndarray:
+        """L1Scoring::score(a[i], b[i]) for a batch of pairs in one call; a vector is (word ids, values)
+        as numpy arrays or device tensors, or a BowVec (BowDatabase.vector_device).  Returns f64 [n]."""
+        import torch
+        n = len(a)
+        if len(b) != n:
+            raise GfplError(-1, "bowScore: a and b differ in length")
+        dev = torch.device("cuda", self.device)
+        keep = []
+
+        def vec(v):
+            if isinstance(v, BowVec):
+                return v
+            i, x = v
+            if isinstance(i, np.ndarray):
+                i = torch.from_numpy(np.ascontiguousarray(i, np.int32)).to(dev)
+                x = torch.from_numpy(np.ascontiguousarray(x, np.float64)).to(dev)
+            keep.append((i, x))
+            return BowVec(_ptr(i) if len(i) else None, _ptr(x) if len(i) else None, len(i))
+
+        va = (BowVec * max(n, 1))(*[vec(v) for v in a])
+        vb = (BowVec * max(n, 1))(*[vec(v) for v in b])
+        out = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        check(self.L.gfpl_bow_score(self.h, va, vb, n, _ptr(out)), "bow_score")
+        return out.cpu().numpy()[:n].copy()
 
     def close(self):
         """gfpl_destroy.  Refused (GfplError, the handle kept) while a StereoFrameHandler
@@ -1619,6 +1723,206 @@ class StereoDetector:
     def close(self):
         if getattr(self, "h", None):
             self.L.gfpl_detector_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ------------------------------------------ loop-closure candidate search --
+class Vocabulary:
+    """gfpl_vocab: a DBoW2 TemplatedVocabulary<FORB> on the device.  Flat arrays: child_off
+    [n_nodes + 1] / child (each node's children in Node::children order, node 0 the root), desc
+    [n_nodes][32] u8, weight [n_nodes] f64, word_id [n_nodes] (-1 on inner nodes).  ctx may be None
+    for the host-side validation alone (it then raises GfplError -1 after the tree passed)."""
+
+    def __init__(self, ctx: Optional[Context], child_off, child, desc, weight, word_id, weighting: int = BOW_TF_IDF,
+                 scoring: int = BOW_L1_NORM):
+        self.L = ctx.L if ctx is not None else hiplib()
+        self.child_off = np.ascontiguousarray(child_off, np.int32)
+        self.child = np.ascontiguousarray(child, np.int32)
+        self.desc = np.ascontiguousarray(desc, np.uint8)
+        self.weight = np.ascontiguousarray(weight, np.float64)
+        self.word_id = np.ascontiguousarray(word_id, np.int32)
+        self.weighting, self.scoring = int(weighting), int(scoring)
+        n = len(self.child_off) - 1
+        if self.desc.size != 32 * n or len(self.weight) != n or len(self.word_id) != n:
+            raise ValueError("Vocabulary: desc, weight and word_id want one row per node")
+        if n < 0 or len(self.child) < int(self.child_off.max()):
+            raise ValueError("Vocabulary: child is shorter than child_off says")
+        child = self.child if len(self.child) else np.zeros(1, np.int32)
+        d = VocabDesc(n, self.child_off.ctypes.data, child.ctypes.data, self.desc.ctypes.data, self.weight.ctypes.data,
+                      self.word_id.ctypes.data, self.weighting, self.scoring)
+        h = C.c_void_p()
+        check(self.L.gfpl_vocab_create(ctx.h if ctx is not None else None, C.byref(d), C.byref(h)), "vocab_create")
+        self.h = h
+
+    @staticmethod
+    def parse_text(path: str):
+        """TemplatedVocabulary::loadFromTextFile's format (TemplatedVocabulary.h:1338-1424): the first
+        line `k L scoring weighting`, then one node per line, `parent isLeaf b0 ... b31 weight`; node ids
+        count up from 1 in file order (0 is the root), a node's children come in file order, word ids
+        count up over the lines with isLeaf > 0.  Blank lines are skipped.  Returns the arrays
+        Vocabulary takes, as a dict."""
+        with open(path) as f:
+            lines = f.read().split("\n")
+        k, L, scoring, weighting = [int(x) for x in lines[0].split()[:4]]
+        if k < 0 or k > 20 or L < 1 or L > 10 or scoring < 0 or scoring > 5 or weighting < 0 or weighting > 3:
+            raise ValueError("Vocabulary.from_text: not a vocabulary text file")
+        parent, desc, weight, word_id = [0], [[0] * 32], [0.0], [-1]
+        n_words = 0
+        for ln in lines[1:]:
+            t = ln.split()
+            if not t:
+                continue
+            if len(t) < 35:
+                raise ValueError("Vocabulary.from_text: short node line")
+            parent.append(int(t[0]))
+            desc.append([int(x) for x in t[2:34]])
+            weight.append(float(t[34]))
+            if int(t[1]) > 0:
+                word_id.append(n_words)
+                n_words += 1
+            else:
+                word_id.append(-1)
+        n = len(parent)
+        kids = [[] for _ in range(n)]
+        for i in range(1, n):
+            if not 0 <= parent[i] < i:
+                raise ValueError("Vocabulary.from_text: a node's parent must come before it")
+            kids[parent[i]].append(i)
+        child_off = np.zeros(n + 1, np.int32)
+        child_off[1:] = np.cumsum([len(c) for c in kids])
+        child = np.array([c for cs in kids for c in cs], np.int32)
+        return dict(child_off=child_off, child=child, desc=np.array(desc, np.uint8), weight=np.array(weight, np.float64),
+                    word_id=np.array(word_id, np.int32), weighting=weighting, scoring=scoring)
+
+    @classmethod
+    def from_text(cls, ctx: Optional[Context], path: str) -> "Vocabulary":
+        return cls(ctx, **cls.parse_text(path))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gfpl_vocab_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bowStats(pl, spl, epl) -> BowStats:
+    """gfpl_kf_bow_stats: vector_stdv of a keyframe's point positions pl [n_pt][2] and line midpoints
+    (spl + epl) * 0.5 [n_ls][2] (src/mapHandler.cpp:2940-2972), on the host."""
+    pl = np.ascontiguousarray(pl, np.float64).reshape(-1, 2)
+    spl = np.ascontiguousarray(spl, np.float64).reshape(-1, 2)
+    epl = np.ascontiguousarray(epl, np.float64).reshape(-1, 2)
+    if len(spl) != len(epl):
+        raise ValueError("bowStats: spl and epl differ in length")
+    out = BowStats()
+    pad = np.zeros((1, 2))
+    check(hiplib().gfpl_kf_bow_stats((pl if len(pl) else pad).ctypes.data, len(pl), (spl if len(spl) else pad).ctypes.data,
+                                     (epl if len(epl) else pad).ctypes.data, len(spl), C.byref(out)), "kf_bow_stats")
+    return out
+
+
+def lookForLoopCandidates(conf_col, alive, graph_col, kf_curr_idx: int, params: Optional[LcSearchParams] = None):
+    """MapHandler::lookForLoopCandidates (src/mapHandler.cpp:3002-3076) on the host: conf_col[i] =
+    conf_matrix[i][kf_curr_idx], alive[i] = map_keyframes[i] != NULL, graph_col[i] =
+    full_graph[i][kf_curr_idx].  Returns (is_lc_candidate, kf_prev_idx, LcSearchInfo)."""
+    n = max(int(kf_curr_idx), 1)
+    cc = np.zeros(n, np.float64)
+    al = np.zeros(n, np.uint8)
+    gr = np.zeros(n, np.int32)
+    k = max(int(kf_curr_idx), 0)
+    cc[:k] = np.asarray(conf_col, np.float64)[:k]
+    al[:k] = np.asarray(alive)[:k] != 0
+    gr[:k] = np.asarray(graph_col, np.int32)[:k]
+    prm = params if params is not None else LcSearchParams.default()
+    prev, info = C.c_int(-1), LcSearchInfo()
+    r = hiplib().gfpl_kf_loop_candidates(cc.ctypes.data, al.ctypes.data, gr.ctypes.data, int(kf_curr_idx), C.byref(prm),
+                                         C.byref(prev), C.byref(info))
+    if r < 0:
+        raise GfplError(r, "kf_loop_candidates")
+    return bool(r), prev.value, info
+
+
+class BowDatabase:
+    """gfpl_bowdb: the BowVectors of the map's keyframes on the device and a row of the confusion
+    matrix per insert (MapHandler::insertKFBowVectorP / L / PL, src/mapHandler.cpp:2865-3000)."""
+
+    def __init__(self, ctx: Context, voc_p: Optional[Vocabulary], voc_l: Optional[Vocabulary], mode: int, kf_cap: int,
+                 pt_cap: int, ls_cap: int):
+        self.L = ctx.L
+        self.ctx, self.mode, self.kf_cap, self.cap = ctx, mode, kf_cap, (pt_cap, ls_cap)
+        self.voc = (voc_p, voc_l)   # they must outlive the database
+        h = C.c_void_p()
+        check(self.L.gfpl_bowdb_create(ctx.h, voc_p.h if voc_p else None, voc_l.h if voc_l else None, mode, kf_cap,
+                                       pt_cap, ls_cap, C.byref(h)), "bowdb_create")
+        self.h = h
+
+    def insert(self, kf_idx: int, kf=None, stats: Optional[BowStats] = None, row: Optional[np.ndarray] = None,
+               pdesc=None, ldesc=None) -> np.ndarray:
+        """gfpl_bowdb_insert.  kf: a KeyFrameView (device arrays), or give the device u8 tensors pdesc /
+        ldesc [n][32] alone.  row: f64 array of at least kf_idx + 1 entries to write into (entries of
+        erased or never-inserted keyframes keep what it held); default zeros.  Returns row[:kf_idx + 1]."""
+        import torch
+        if kf is not None:
+            v = kf.s if isinstance(kf, KeyFrameView) else kf
+        else:
+            v = KFViewStruct()
+            for n_f, p_f, t in (("n_pt", "pdesc", pdesc), ("n_ls", "ldesc", ldesc)):
+                if t is not None and int(t.shape[0]):
+                    setattr(v, n_f, int(t.shape[0]))
+                    setattr(v, p_f, _ptr(t))
+        if row is None:
+            row = np.zeros(max(kf_idx, 0) + 1, np.float64)
+        if row.dtype != np.float64 or not row.flags.c_contiguous or len(row) < kf_idx + 1:
+            raise ValueError("BowDatabase.insert: row wants a contiguous f64 array of kf_idx + 1 entries")
+        torch.cuda.synchronize()
+        check(self.L.gfpl_bowdb_insert(self.h, kf_idx, C.byref(v), C.byref(stats) if stats is not None else None,
+                                       row.ctypes.data), "bowdb_insert")
+        return row[:kf_idx + 1]
+
+    def _mode_insert(self, mode, kf_idx, kf, stats, row, pdesc, ldesc):
+        if self.mode != mode:
+            raise GfplError(-1, "BowDatabase: created in another mode")
+        return self.insert(kf_idx, kf, stats, row, pdesc, ldesc)
+
+    def insertKFBowVectorP(self, kf_idx: int, kf=None, row=None, pdesc=None):
+        return self._mode_insert(BOW_MODE_P, kf_idx, kf, None, row, pdesc, None)
+
+    def insertKFBowVectorL(self, kf_idx: int, kf=None, row=None, ldesc=None):
+        return self._mode_insert(BOW_MODE_L, kf_idx, kf, None, row, None, ldesc)
+
+    def insertKFBowVectorPL(self, kf_idx: int, kf=None, stats: Optional[BowStats] = None, row=None, pdesc=None, ldesc=None):
+        return self._mode_insert(BOW_MODE_PL, kf_idx, kf, stats, row, pdesc, ldesc)
+
+    def erase(self, kf_idx: int):
+        """map_keyframes[kf_idx] = NULL as the database sees it"""
+        check(self.L.gfpl_bowdb_erase(self.h, kf_idx), "bowdb_erase")
+
+    def vector_device(self, kind: int, kf_idx: int) -> BowVec:
+        """the stored vector (kind 0: descDBoW_P, 1: descDBoW_L) as a device triple"""
+        v = BowVec()
+        check(self.L.gfpl_bowdb_vector(self.h, kind, kf_idx, C.byref(v), None, None), "bowdb_vector")
+        return v
+
+    def vector(self, kind: int, kf_idx: int):
+        """the stored vector copied to the host: (word ids int32, values f64)"""
+        v = self.vector_device(kind, kf_idx)
+        ids, vals = np.zeros(max(v.count, 1), np.int32), np.zeros(max(v.count, 1), np.float64)
+        check(self.L.gfpl_bowdb_vector(self.h, kind, kf_idx, C.byref(v), ids.ctypes.data, vals.ctypes.data), "bowdb_vector")
+        return ids[:v.count], vals[:v.count]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gfpl_bowdb_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -697,8 +697,9 @@ int  gfpl_kf_local_map_matches(gfpl_ctx* ctx, const gfpl_map_view* map, const gf
  * its best match (no ratio and no MAD test), pairs in kf0 row order; the features take the
  * class-default sigma2 = 1.0 and inlier = true; Config::maxIters Gauss-Newton iterations from
  * T_inc = I over the point and line residuals of kf0's 3D under T_inc against kf1's
- * observations; the chi-square outlier pass (sqrt(7.815)); the five gates below.  The DBoW2
- * candidate search and the pose graph stay with the caller.  T_kf_w, pt_sigma2 and ls_sigma2
+ * observations; the chi-square outlier pass (sqrt(7.815)); the five gates below.  The candidates
+ * come from gfpl_bowdb_insert + gfpl_kf_loop_candidates (below); the pose graph stays with the
+ * caller.  T_kf_w, pt_sigma2 and ls_sigma2
  * of the views are not read.  A kind with fewer than two rows on either keyframe yields no
  * pairs (ledger U4).                                                                       */
 typedef struct gfpl_loop_params { double lc_res, lc_unc, lc_inl, lc_trs, lc_rot; } gfpl_loop_params;
@@ -725,6 +726,118 @@ int  gfpl_kf_loop_closure(gfpl_ctx* ctx, const gfpl_kf_view* kf0, const gfpl_kf_
                           const gfpl_loop_params* prm, int pt_cap, int ls_cap,
                           int32_t* pt_pairs, uint8_t* pt_inlier, int32_t* ls_pairs, uint8_t* ls_inlier,
                           gfpl_loop_result* out);
+
+/* ------------------------------------- loop-closure candidate search ----- */
+/* DBoW2 as MapHandler uses it (insertKFBowVectorP / L / PL, src/mapHandler.cpp:2865-3000, and
+ * lookForLoopCandidates, :3002-3076): TemplatedVocabulary<FORB>::transform and L1Scoring::score
+ * on the device (k_bow.hip), the keyframe database around them, and the decision over a row of
+ * the confusion matrix on the host.  Every double has the reference's bits (DESIGN.md ledger
+ * BW1-BW8).                                                                                   */
+typedef struct gfpl_vocab gfpl_vocab;
+typedef struct gfpl_bowdb gfpl_bowdb;
+/* DBoW2::WeightingType / ScoringType */
+#define GFPL_BOW_TF_IDF 0
+#define GFPL_BOW_TF     1
+#define GFPL_BOW_IDF    2
+#define GFPL_BOW_BINARY 3
+#define GFPL_BOW_L1_NORM 0
+/* A vocabulary tree as flat HOST arrays (both of DBoW2's file formats fit: the .yml names node
+ * and word ids, the text format implies them).  Node 0 is the root.  child[child_off[i] ..
+ * child_off[i + 1]) are node i's children in Node::children order (the descent walks them in
+ * that order, the first minimum wins); a node without children is a leaf and ends the descent
+ * (the tree may be ragged).  word_id is read on leaves only (-1 on inner nodes).             */
+typedef struct gfpl_vocab_desc {
+    int            n_nodes;
+    const int32_t* child_off;   /* [n_nodes + 1], ascending from 0                            */
+    const int32_t* child;       /* [child_off[n_nodes]] node indices                          */
+    const uint8_t* desc;        /* [n_nodes][32] (the root's row is never read)               */
+    const double*  weight;      /* [n_nodes]                                                  */
+    const int32_t* word_id;     /* [n_nodes]                                                  */
+    int            weighting;   /* GFPL_BOW_TF_IDF ... GFPL_BOW_BINARY                        */
+    int            scoring;     /* GFPL_BOW_L1_NORM                                           */
+} gfpl_vocab_desc;
+/* Validates on the host, before the context is looked at, then uploads the device copy.
+ * GFPL_E_INVALID: NULL array, n_nodes < 2, a root without children (the reference indexes
+ * children[0] of it), child_off not ascending from 0, a child index outside [1, n_nodes), a node
+ * reachable twice or a cycle, a leaf with word_id < 0, a word id on two leaves, a weighting
+ * outside 0..3, a NULL context.  GFPL_E_UNSUPPORTED: a node with more than 32 children, a scoring
+ * other than L1_NORM.  GFPL_E_NOMEM: the device copy could not be allocated.  Nodes the root does
+ * not reach are ignored.  The context cannot be destroyed while the vocabulary lives.        */
+int  gfpl_vocab_create(gfpl_ctx* ctx, const gfpl_vocab_desc* desc, gfpl_vocab** out);
+/* the host-side rules alone (no context, no device): GFPL_OK or the code gfpl_vocab_create returns */
+int  gfpl_vocab_check(const gfpl_vocab_desc* desc);
+int  gfpl_vocab_destroy(gfpl_vocab* voc);
+
+#define GFPL_BOW_MAX_CAP 8192   /* descriptors per set (the set's keys are sorted in 32 KB of LDS) */
+/* TemplatedVocabulary::transform(features, BowVector&) (TemplatedVocabulary.h:1065-1122) for n
+ * descriptor sets in one call.  desc_ptrs / counts: HOST arrays of n DEVICE pointers ([counts[i]][32]
+ * bytes, 16-byte aligned) and row counts.  Outputs (device): word_ids [n][cap] int32 and values
+ * [n][cap] double, set i's first n_words[i] entries in ascending word id (std::map's order); n_words:
+ * host [n].  GFPL_E_CAPACITY, nothing launched, when a count exceeds cap; GFPL_E_UNSUPPORTED for
+ * cap > GFPL_BOW_MAX_CAP; n = 0 is GFPL_OK.  Synchronises.                                     */
+int  gfpl_bow_transform(gfpl_ctx* ctx, const gfpl_vocab* voc, int n, const uint8_t* const* desc_ptrs,
+                        const int* counts, int cap, int32_t* word_ids, double* values, int* n_words);
+
+/* a BowVector on the device: count entries in ascending word id */
+typedef struct gfpl_bow_vec { const int32_t* ids; const double* values; int count; } gfpl_bow_vec;
+/* L1Scoring::score(a[i], b[i]) (ScoringObject.cpp:23-68) for n_pairs pairs; a, b: HOST arrays of
+ * device triples; scores: DEVICE [n_pairs].  Two vectors without a common word score -0.0.
+ * Synchronises.                                                                                */
+int  gfpl_bow_score(gfpl_ctx* ctx, const gfpl_bow_vec* a, const gfpl_bow_vec* b, int n_pairs, double* scores);
+
+/* vector_stdv (src/auxiliar.cpp:547-556) of a keyframe's features as insertKFBowVectorPL takes
+ * it (:2940-2947, :2961-2972): std_pt over the x and the y of pl, std_ls over the midpoints
+ * (spl + epl) * 0.5.  Host arrays [n][2]; zero rows give 0/0 as in the reference (NaN).      */
+typedef struct gfpl_bow_stats { int32_t n_pt, n_ls; double std_pt, std_ls; } gfpl_bow_stats;
+int  gfpl_kf_bow_stats(const double* pl, int n_pt, const double* spl, const double* epl, int n_ls,
+                       gfpl_bow_stats* out);
+
+#define GFPL_BOW_MODE_P  0   /* insertKFBowVectorP  */
+#define GFPL_BOW_MODE_L  1   /* insertKFBowVectorL  */
+#define GFPL_BOW_MODE_PL 2   /* insertKFBowVectorPL */
+/* The BowVectors of up to kf_cap keyframes, resident on the device (KeyFrame::descDBoW_P / _L).
+ * voc_l may be NULL in mode P and voc_p in mode L; pt_cap / ls_cap: descriptor rows per keyframe
+ * (<= GFPL_BOW_MAX_CAP).  The vocabularies must outlive the database.                        */
+int  gfpl_bowdb_create(gfpl_ctx* ctx, const gfpl_vocab* voc_p, const gfpl_vocab* voc_l, int mode, int kf_cap,
+                       int pt_cap, int ls_cap, gfpl_bowdb** out);
+int  gfpl_bowdb_destroy(gfpl_bowdb* db);
+/* insertKFBowVectorP / L / PL for keyframe kf_idx: transforms kf's pdesc / ldesc (only n_pt / pdesc
+ * and n_ls / ldesc of the view are read), stores the vectors, scores them against every stored
+ * keyframe i < kf_idx in one launch and writes row[i] (HOST, kf_idx + 1 doubles: conf_matrix[kf_idx][i])
+ * for those i and for i = kf_idx (the vector against itself); entries of erased or never-inserted
+ * keyframes are left as they are.  Mode PL combines the two scores as :2986-2988 do with stats
+ * (required in mode PL, of the NEW keyframe; ignored otherwise).  kf_idx = 0 stores the vectors and
+ * writes row[0] = 1.0 (MapHandler::initialize).  GFPL_E_INVALID for an index that is negative or was
+ * inserted before, GFPL_E_CAPACITY for kf_idx >= kf_cap or more rows than pt_cap / ls_cap.
+ * Synchronises.                                                                                */
+int  gfpl_bowdb_insert(gfpl_bowdb* db, int kf_idx, const gfpl_kf_view* kf, const gfpl_bow_stats* stats, double* row);
+/* map_keyframes[kf_idx] = NULL as the database sees it: later inserts skip it                  */
+int  gfpl_bowdb_erase(gfpl_bowdb* db, int kf_idx);
+/* the stored vector of a live keyframe; kind 0 = points (descDBoW_P), 1 = lines (descDBoW_L): the
+ * device triple in *out and, where ids_host / values_host are not NULL, a host copy of its
+ * out->count entries (the copy synchronises)                                                    */
+int  gfpl_bowdb_vector(const gfpl_bowdb* db, int kind, int kf_idx, gfpl_bow_vec* out, int32_t* ids_host,
+                       double* values_host);
+
+/* Config::lcKFDist, lcKFMaxDist, lcNKFClosest, minLMCovGraph, minKFLocalMap                    */
+typedef struct gfpl_lc_search_params {
+    int32_t lc_kf_dist, lc_kf_max_dist, lc_nkf_closest, min_lm_cov_graph, min_kf_local_map;
+} gfpl_lc_search_params;
+/* 100, 20, 4, 30, 3 (src/config.cpp:68-70, 51, 53) */
+void gfpl_default_lc_search_params(gfpl_lc_search_params* prm);
+typedef struct gfpl_lc_search_info {
+    double  lc_min_score;
+    int32_t nkf_closest, idx_max;   /* idx_max = -1 when the size gate fails                     */
+    int32_t n_list, pad;            /* entries of max_confmat                                    */
+} gfpl_lc_search_info;
+/* MapHandler::lookForLoopCandidates (:3002-3076), host only: conf_col[i] = conf_matrix[i][kf_curr_idx],
+ * alive[i] != 0 where map_keyframes[i] != NULL, graph_col[i] = full_graph[i][kf_curr_idx], each of
+ * kf_curr_idx entries.  std::sort orders the list, so equal scores fall as they do in the reference.
+ * Returns 1 (candidate, *kf_prev_idx set) or 0 (*kf_prev_idx = -1); GFPL_E_INVALID for a NULL
+ * pointer, kf_curr_idx < 0 or a negative parameter.  info may be NULL.                          */
+int  gfpl_kf_loop_candidates(const double* conf_col, const uint8_t* alive, const int32_t* graph_col,
+                             int kf_curr_idx, const gfpl_lc_search_params* prm, int* kf_prev_idx,
+                             gfpl_lc_search_info* info);
 
 /* ----------------------------------------------------- state transfer ----- */
 /* Copy one sequence's frame state device -> host (synchronises).            */
