@@ -74,6 +74,7 @@ struct gfpl_event {
 int gfpl_ctx_device(const gfpl_ctx* c) { return c->device; }
 void* gfpl_ctx_stream(const gfpl_ctx* c) { return (void*)c->stream; }
 const gfpl_camera* gfpl_ctx_camera(const gfpl_ctx* c) { return c->has_cam ? &c->cam : nullptr; }
+const gfpl_config* gfpl_ctx_config(const gfpl_ctx* c) { return &c->cfg; }
 int64_t gfpl_event_records(const gfpl_event* e) { return e->records; }
 void gfpl_ctx_attach(gfpl_ctx* c) { c->n_detectors.fetch_add(1); }
 void gfpl_ctx_detach(gfpl_ctx* c) { c->n_detectors.fetch_sub(1); }

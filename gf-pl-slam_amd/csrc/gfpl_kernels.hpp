@@ -138,6 +138,29 @@ hipError_t launch_bow_transform(const BowVocabDev& v, const BowSet* sets, int n,
                                 int32_t* word_ids, double* values, int32_t* n_words, hipStream_t s);
 hipError_t launch_bow_score(const BowPair* pairs, int n, double* scores, hipStream_t s);
 
+// levMarquardtOptimizationLBA (k_lba.hip): one problem; all pointers device.  lm_start / obs_lm /
+// obs_kf are LbaMem's uploaded index arrays over the unified landmark and observation numbering.
+struct LbaProb {
+    gfpl_lba_counts n;
+    const double* x_kf;
+    double* T_kf;
+    const double* T_fix;
+    double *pt, *ls;
+    const double *pt_obs, *pt_sigma, *ls_obs, *ls_sigma;
+    double* x_out;
+    const int32_t *lm_start, *obs_lm, *obs_kf;
+    LbaPtrs m;
+};
+struct LbaArgs {
+    DevCam cam;                   // fx, fy, cx, cy are read
+    double homog_th;
+    gfpl_lba_params prm;
+    const LbaProb* probs;         // [n]
+    gfpl_lba_result* out;         // [n]
+    int lds_kfs;                  // the largest n_kf of the launch (LbaLds)
+};
+hipError_t launch_lba(const LbaArgs& a, int n, hipStream_t s);
+
 }  // namespace gfpl
 
 namespace gfpl {
@@ -153,6 +176,7 @@ void pyrbuild_destroy(PyrBuild* pb);
 int gfpl_ctx_device(const gfpl_ctx* c);
 void* gfpl_ctx_stream(const gfpl_ctx* c);
 const gfpl_camera* gfpl_ctx_camera(const gfpl_ctx* c);   // NULL before gfpl_set_camera
+const gfpl_config* gfpl_ctx_config(const gfpl_ctx* c);
 // a detector created on the context counts itself in until it is destroyed (gfpl_destroy refuses meanwhile)
 void gfpl_ctx_attach(gfpl_ctx* c);
 void gfpl_ctx_detach(gfpl_ctx* c);

@@ -252,4 +252,64 @@ struct BowFinishLds {
     GFPL_HD BowFinishLds(unsigned char* smem, int p2, int max_count) : c(smem), p2(p2), max_count(max_count) {}
 };
 
+// ---- local bundle adjustment (k_lba.hip, gfpl_lba.cpp): one problem's device workspace.
+// Landmarks are numbered points first, then lines; a point block has 3 rows, a line block 6.
+// A coupling block W (and Y = V^-1 W) is [landmark rows][6 pose columns], one per landmark and
+// local keyframe; only the keyframes of the landmark's mask are ever read.
+constexpr int LBA_BLOCK = 256;    // threads of k_lba = observation rows per LDS chunk
+constexpr int LBA_ROW = 14;       // doubles per observation row: J_pose[6], J_landmark[6], |err|, w
+constexpr int LBA_MAX_KFS = 16;   // = GFPL_LBA_MAX_KFS (gfpl_lba.cpp asserts it)
+struct LbaPtrs {
+    double *X, *DX;               // [6 n_kf + 3 n_pt + 6 n_ls]
+    double* rows;                 // [n_obs][LBA_ROW], points first
+    double *U, *gk;               // [n_kf][36], [n_kf][6]: undamped pose blocks and their gradient
+    double *V, *Vi;               // [9 n_pt + 36 n_ls]: undamped landmark blocks, inverses of the damped ones
+    double *glm, *z;              // [3 n_pt + 6 n_ls]: landmark gradient, V^-1 g
+    double *W, *Y;                // [n_kf (18 n_pt + 36 n_ls)]
+    double* q;                    // [n_lm] squared step of each landmark
+    int32_t* mask;                // [n_lm] bit s: local keyframe s observes the landmark
+    int32_t* state;               // [8]: 0 the last iteration evaluated
+};
+struct LbaMem {
+    Carver c;
+    int nkf, npt, nls, nobs;
+    size_t N = 6 * (size_t)nkf + 3 * (size_t)npt + 6 * (size_t)nls;
+    size_t nv = 9 * (size_t)npt + 36 * (size_t)nls, ng = 3 * (size_t)npt + 6 * (size_t)nls;
+    size_t nw = (size_t)nkf * (18 * (size_t)npt + 36 * (size_t)nls);
+    LbaPtrs p{c.take<double>(N), c.take<double>(N), c.take<double>((size_t)nobs * LBA_ROW),
+              c.take<double>((size_t)nkf * 36), c.take<double>((size_t)nkf * 6),
+              c.take<double>(nv), c.take<double>(nv), c.take<double>(ng), c.take<double>(ng),
+              c.take<double>(nw), c.take<double>(nw), c.take<double>((size_t)npt + nls),
+              c.take<int32_t>((size_t)npt + nls), c.take<int32_t>(8)};
+    // the uploaded index arrays: first observation of each landmark, then per observation its landmark and slot
+    int32_t* lm_start = c.take<int32_t>((size_t)npt + nls + 1);
+    int32_t* obs_lm = c.take<int32_t>((size_t)nobs);
+    int32_t* obs_kf = c.take<int32_t>((size_t)nobs);
+    size_t bytes = (c.off + 255) & ~(size_t)255;
+    LbaMem(char* base, int nkf, int npt, int nls, int nobs) : c{0, base}, nkf(nkf), npt(npt), nls(nls), nobs(nobs) {}
+};
+
+// ---- k_lba: the reduced pose system S (6 n_kf square, lower triangle used) with its right-hand
+// side, pivots and solution, the inverse poses of the iteration, one chunk of observation rows
+// with their slots, a reduction buffer and the loop's state.  kfs is the launch's largest n_kf.
+struct LbaLds {
+    LdsCarver c;
+    int kfs;
+    double* S = c.take<double>(36 * kfs * kfs);
+    double* gr = c.take<double>(6 * kfs);
+    double* D = c.take<double>(6 * kfs);
+    double* dx = c.take<double>(6 * kfs);
+    double* Tinv = c.take<double>(16 * kfs);
+    double* rows = c.take<double>(LBA_BLOCK * LBA_ROW);
+    double* red = c.take<double>(LBA_BLOCK);
+    double* sd = c.take<double>(8);      // lambda, err, err_prev, err sum, |DX|^2
+    int* slot = c.take<int>(LBA_BLOCK);
+    int* si = c.take<int>(16);           // iters, stop, status, hmax, done, singular, accept
+    int bytes = c.off;
+    GFPL_HD LbaLds(unsigned char* smem, int kfs) : c(smem), kfs(kfs) {}
+};
+static_assert(8 * (36 * LBA_MAX_KFS * LBA_MAX_KFS + 34 * LBA_MAX_KFS + LBA_BLOCK * (LBA_ROW + 1) + 8) + 4 * (LBA_BLOCK + 16) <=
+                  160 * 1024 - 1024,
+              "LbaLds at LBA_MAX_KFS must fit a workgroup's dynamic LDS");
+
 }  // namespace gfpl

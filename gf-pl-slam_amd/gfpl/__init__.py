@@ -237,6 +237,99 @@ class LoopResult(C.Structure):
                 ("T_inc", C.c_double * 16)]
 
 
+LBA_MAX_KFS = 16   # GFPL_LBA_MAX_KFS
+LBA_STOP_ITERS, LBA_STOP_DERR, LBA_STOP_ERR, LBA_STOP_STEP = 0, 1, 2, 3
+LBA_SINGULAR, LBA_HMAX_RANGE = 1, 2
+
+
+class LbaParams(C.Structure):
+    """gfpl_lba_params: Config::lambdaLbaLM / lambdaLbaK / maxItersLba (src/config.cpp:55-57);
+    LbaParams.default() fills the reference's values."""
+    _fields_ = [("lambda_lm", C.c_double), ("lambda_k", C.c_double), ("max_iters", C.c_int32), ("pad", C.c_int32)]
+
+    @classmethod
+    def default(cls, **over) -> "LbaParams":
+        p = cls()
+        hiplib().gfpl_default_lba_params(C.byref(p))
+        for k, v in over.items():
+            setattr(p, k, v)
+        return p
+
+
+class LbaCounts(C.Structure):
+    _fields_ = [("n_kf", C.c_int32), ("n_fix", C.c_int32), ("n_pt", C.c_int32), ("n_ls", C.c_int32),
+                ("n_pt_obs", C.c_int32), ("n_ls_obs", C.c_int32)]
+
+
+class LbaProblemStruct(C.Structure):
+    _fields_ = [("n", LbaCounts)] + [(k, _vp) for k in (
+        "x_kf", "T_kf", "T_fix", "pt", "ls", "pt_obs", "pt_sigma", "ls_obs", "ls_sigma", "x_out",
+        "pt_obs_lm", "pt_obs_kf", "ls_obs_lm", "ls_obs_kf")]
+
+
+class LbaResult(C.Structure):
+    """gfpl_lba_result: iters is the reference's loop variable at exit; stop LBA_STOP_*; status bits
+    LBA_SINGULAR / LBA_HMAX_RANGE; hmax the truncated largest diagonal; lambda, err, err_prev at exit."""
+    _fields_ = [("iters", C.c_int32), ("stop", C.c_int32), ("status", C.c_int32), ("hmax", C.c_int32),
+                ("lambda_", C.c_double), ("err", C.c_double), ("err_prev", C.c_double)]
+
+
+LBA_DOUBLES = [("x_kf", 6), ("T_kf", 16), ("T_fix", 16), ("pt", 3), ("ls", 6), ("pt_obs", 2), ("pt_sigma", 1),
+               ("ls_obs", 3), ("ls_sigma", 1)]
+LBA_INDICES = ["pt_obs_lm", "pt_obs_kf", "ls_obs_lm", "ls_obs_kf"]
+
+
+class LbaProblem:
+    """One local bundle adjustment (gfpl_lba_problem) from numpy arrays: x_kf [n_kf][6] and T_kf
+    [n_kf][4][4] (KeyFrame::x_kf_w and T_kf_w of the local keyframes, which the reference reads
+    separately), T_fix [n_fix][4][4], pt [n_pt][3], ls [n_ls][6], and per observation its local
+    landmark (pt_obs_lm), keyframe slot (pt_obs_kf: >= 0 local keyframe, -1 - f fixed pose f), the
+    observation (pt_obs [.][2], ls_obs [.][3]) and sigma.  A landmark's observations are contiguous.
+    The arrays are kept as given (float64 / int32 copies); check() runs gfpl_lba_check on them."""
+
+    def __init__(self, x_kf, T_kf, T_fix, pt, ls, pt_obs_lm, pt_obs_kf, pt_obs, pt_sigma, ls_obs_lm, ls_obs_kf,
+                 ls_obs, ls_sigma):
+        loc = locals()
+        self.a = {}
+        for k, w in LBA_DOUBLES:
+            self.a[k] = np.ascontiguousarray(np.asarray(loc[k], np.float64).reshape(-1, w))
+        for k in LBA_INDICES:
+            self.a[k] = np.ascontiguousarray(np.asarray(loc[k], np.int32).reshape(-1))
+        self.counts = LbaCounts(len(self.a["x_kf"]), len(self.a["T_fix"]), len(self.a["pt"]), len(self.a["ls"]),
+                                len(self.a["pt_obs_lm"]), len(self.a["ls_obs_lm"]))
+
+    def struct(self, dev=None) -> LbaProblemStruct:
+        """The C record: index arrays on the host; the doubles on the host (dev=None, for check()) or
+        the device tensors of `dev` (a dict name -> tensor)."""
+        s = LbaProblemStruct()
+        s.n = self.counts
+        for k in LBA_INDICES:
+            setattr(s, k, _ptr(self.a[k]) if len(self.a[k]) else None)
+        for k, _ in LBA_DOUBLES:
+            src = self.a[k] if dev is None else dev[k]
+            setattr(s, k, _ptr(src) if len(self.a[k]) else None)
+        if dev is not None:
+            s.x_out = _ptr(dev["x_out"])
+        return s
+
+    def check(self) -> int:
+        return hiplib().gfpl_lba_check(C.byref(self.struct()))
+
+    def workspace(self):
+        """(hbm_bytes, lds_bytes) of gfpl_lba_workspace."""
+        hbm, lds = C.c_int64(0), C.c_int32(0)
+        check(hiplib().gfpl_lba_workspace(C.byref(self.counts), C.byref(hbm), C.byref(lds)), "lba_workspace")
+        return hbm.value, lds.value
+
+
+def lbaWorkspace(n_kf, n_fix, n_pt, n_ls, n_pt_obs, n_ls_obs):
+    """gfpl_lba_workspace: (return code, hbm_bytes, lds_bytes) for one problem of these counts."""
+    hbm, lds = C.c_int64(0), C.c_int32(0)
+    cnt = LbaCounts(n_kf, n_fix, n_pt, n_ls, n_pt_obs, n_ls_obs)
+    rc = hiplib().gfpl_lba_workspace(C.byref(cnt), C.byref(hbm), C.byref(lds))
+    return rc, hbm.value, lds.value
+
+
 # DBoW2::WeightingType and the keyframe database's modes (include/gfpl.h)
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
@@ -526,6 +619,13 @@ def hiplib() -> C.CDLL:
             "gfpl_rectify_stereo_async": ([P, P, P, C.c_int, P, P], C.c_int),
             "gfpl_rectify_host": ([P, C.c_int, P, C.c_int, P], C.c_int),
             "gfpl_detector_set_rectifier": ([P, P], C.c_int),
+            "gfpl_default_lba_params": ([P], None),
+            "gfpl_lba_check": ([P], C.c_int),
+            "gfpl_lba_workspace": ([P, P, P], C.c_int),
+            "gfpl_lba_create": ([P, P, C.c_int, C.POINTER(P)], C.c_int),
+            "gfpl_lba_destroy": ([P], C.c_int),
+            "gfpl_lba_solve": ([P, P, C.c_int, P, P], C.c_int),
+            "gfpl_lba_debug_system": ([P, C.c_int, C.c_int, P, P, P, P, P, P, P], C.c_int),
         }
         for n, (a, r) in sigs.items():
             try:
@@ -1044,6 +1144,35 @@ class Context:
         check(self.L.gfpl_bow_score(self.h, va, vb, n, _ptr(out)), "bow_score")
         return out.cpu().numpy()[:n].copy()
 
+    def _lba_run(self, problems, prm, debug=None):
+        caps = [max([getattr(p.counts, f) for p in problems] + [1 if f == "n_kf" else 0]) for f, _ in LbaCounts._fields_]
+        for p in problems:   # the host rules first: nothing is allocated for a refused problem
+            rc = p.check()
+            if rc != 0:
+                raise GfplError(rc, "lba_check")
+        solver = LbaSolver(self, caps, max(len(problems), 1))
+        try:
+            return solver.solve(problems, prm, debug)
+        finally:
+            solver.close()
+
+    def localBundleAdjustment(self, problems, params: Optional[LbaParams] = None):
+        """MapHandler::localBundleAdjustment's solver (levMarquardtOptimizationLBA, src/mapHandler.cpp:
+        1217-1713) for a batch of LbaProblem in one call (a single problem may be passed).  Per problem
+        a dict: result (LbaResult), T_kf [n_kf][4][4] = expmap_se3(X), pt, ls and x_kf, the pose part of
+        X at exit.  The problems' own arrays are not changed."""
+        single = isinstance(problems, LbaProblem)
+        res = self._lba_run([problems] if single else list(problems), params if params is not None else LbaParams.default())
+        return res[0] if single else res
+
+    def lbaDebugSystem(self, problem: LbaProblem, iteration: int, params: Optional[LbaParams] = None):
+        """Test hook (gfpl_lba_debug_system): the undamped system of `iteration` (0: the pre-pass) —
+        the pose blocks U, the landmark blocks V_pt / V_ls, the coupling blocks W_pt / W_ls (landmark
+        rows, pose columns), g and err — from a solve of iteration + 1 iterations."""
+        prm = LbaParams.default() if params is None else LbaParams.from_buffer_copy(params)
+        prm.max_iters = iteration + 1
+        return self._lba_run([problem], prm, debug=(0, iteration))[1]
+
     def close(self):
         """gfpl_destroy.  Refused (GfplError, the handle kept) while a StereoFrameHandler
         created on this context is still open: close those first."""
@@ -1087,6 +1216,62 @@ class Event:
     def close(self):
         if getattr(self, "h", None):
             self.L.gfpl_event_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LbaSolver:
+    """gfpl_lba: the device workspace of up to max_problems local bundle adjustments whose counts stay
+    within caps (n_kf, n_fix, n_pt, n_ls, n_pt_obs, n_ls_obs); solve() may be called any number of
+    times.  The context cannot be closed while the solver is open."""
+
+    def __init__(self, ctx: "Context", caps, max_problems: int):
+        self.ctx, self.L = ctx, ctx.L
+        self.caps = caps if isinstance(caps, LbaCounts) else LbaCounts(*[int(v) for v in caps])
+        self.h = C.c_void_p()
+        check(self.L.gfpl_lba_create(ctx.h, C.byref(self.caps), max_problems, C.byref(self.h)), "lba_create")
+
+    def solve(self, problems, params: Optional[LbaParams] = None, debug=None):
+        """Per problem a dict (see Context.localBundleAdjustment).  debug = (i, iteration): also the
+        system of gfpl_lba_debug_system for problem i, as the second element of a pair."""
+        import torch
+        prm = params if params is not None else LbaParams.default()
+        n = len(problems)
+        dev = torch.device("cuda", self.ctx.device)
+        devs, structs = [], (LbaProblemStruct * max(n, 1))()
+        for i, p in enumerate(problems):
+            d = {k: torch.from_numpy(p.a[k].copy()).to(dev) for k, _ in LBA_DOUBLES}
+            d["x_out"] = d["x_kf"].clone()   # (a problem whose Hmax leaves the int range writes nothing)
+            devs.append(d)
+            structs[i] = p.struct(d)
+        out = (LbaResult * max(n, 1))()
+        torch.cuda.synchronize()
+        check(self.L.gfpl_lba_solve(self.h, structs, n, C.byref(prm), out), "lba_solve")
+        res = []
+        for i, d in enumerate(devs):
+            res.append(dict(result=LbaResult.from_buffer_copy(out[i]), T_kf=d["T_kf"].cpu().numpy().reshape(-1, 4, 4),
+                            pt=d["pt"].cpu().numpy(), ls=d["ls"].cpu().numpy(), x_kf=d["x_out"].cpu().numpy()))
+        if debug is None:
+            return res
+        i, it = debug
+        c = problems[i].counts
+        sysd = dict(U=np.zeros((c.n_kf, 6, 6)), g=np.zeros(6 * c.n_kf + 3 * c.n_pt + 6 * c.n_ls),
+                    V_pt=np.zeros((c.n_pt, 3, 3)), V_ls=np.zeros((c.n_ls, 6, 6)),
+                    W_pt=np.zeros((c.n_pt, c.n_kf, 3, 6)), W_ls=np.zeros((c.n_ls, c.n_kf, 6, 6)))
+        err = C.c_double(0.0)
+        check(self.L.gfpl_lba_debug_system(self.h, i, it, *[_ptr(sysd[k]) for k in ("U", "g", "V_pt", "V_ls", "W_pt", "W_ls")],
+                                           C.byref(err)), "lba_debug_system")
+        sysd["err"] = np.float64(err.value)
+        return res, sysd
+
+    def close(self):
+        if getattr(self, "h", None):
+            check(self.L.gfpl_lba_destroy(self.h), "lba_destroy")
             self.h = None
 
     def __del__(self):

@@ -839,6 +839,80 @@ int  gfpl_kf_loop_candidates(const double* conf_col, const uint8_t* alive, const
                              int kf_curr_idx, const gfpl_lc_search_params* prm, int* kf_prev_idx,
                              gfpl_lc_search_info* info);
 
+/* ------------------------------------------- local bundle adjustment ----- */
+/* MapHandler::localBundleAdjustment's solver levMarquardtOptimizationLBA (src/mapHandler.cpp:
+ * 1217-1713) for n problems in one call, one workgroup each (k_lba.hip).  The linearisation, the
+ * accumulation of H, g and err, Hmax, the damping, the stop tests and the lambda rule are the
+ * reference's, quirks included (DESIGN.md ledger BA1-BA14): H, g and err of every iteration
+ * have its bits.  The solve is pinned to our own elimination (landmark blocks first, then a dense
+ * LDL^T of the reduced pose system without pivoting), not to Eigen's SimplicialLDLT.          */
+#define GFPL_LBA_MAX_KFS 16   /* local keyframes per problem: the reduced system (96 x 96 doubles) and a
+                                 chunk of observation rows share one workgroup's LDS (LbaLds)  */
+typedef struct gfpl_lba gfpl_lba;
+/* Config::lambdaLbaLM, lambdaLbaK, maxItersLba: 0.001, 10.0, 20 (src/config.cpp:55-57) */
+typedef struct gfpl_lba_params { double lambda_lm, lambda_k; int32_t max_iters, pad; } gfpl_lba_params;
+void gfpl_default_lba_params(gfpl_lba_params* prm);
+typedef struct gfpl_lba_counts { int32_t n_kf, n_fix, n_pt, n_ls, n_pt_obs, n_ls_obs; } gfpl_lba_counts;
+/* One problem.  The doubles are DEVICE arrays, the four index arrays HOST arrays (they are the
+ * caller's graph bookkeeping; the call checks them before any device work and uploads them).
+ * X = [x_kf | pt | ls] as the reference lays it out.  x_kf is where X starts and T_kf where the
+ * first linearisation is taken: KeyFrame::x_kf_w and KeyFrame::T_kf_w, which the reference reads
+ * separately and which may differ.  An observation's keyframe slot s >= 0 names local keyframe s,
+ * s < 0 the fixed pose -1 - s (a keyframe outside the list, keyframe 0 included).  A landmark's
+ * observations are contiguous: *_obs_lm starts at 0 and rises in steps of 0 or 1 to n - 1.      */
+typedef struct gfpl_lba_problem {
+    gfpl_lba_counts n;
+    const double*  x_kf;        /* [n_kf][6]  in                                               */
+    double*        T_kf;        /* [n_kf][16] in: T_kf_w; out: expmap_se3(X)                   */
+    const double*  T_fix;       /* [n_fix][16]                                                 */
+    double*        pt;          /* [n_pt][3]  in / out: point3D                                */
+    double*        ls;          /* [n_ls][6]  in / out: line3D                                 */
+    const double*  pt_obs;      /* [n_pt_obs][2]                                               */
+    const double*  pt_sigma;    /* [n_pt_obs] sigma_list                                       */
+    const double*  ls_obs;      /* [n_ls_obs][3]                                               */
+    const double*  ls_sigma;    /* [n_ls_obs]                                                  */
+    double*        x_out;       /* [n_kf][6]  out: the pose part of X at exit, or NULL         */
+    const int32_t* pt_obs_lm;   /* HOST [n_pt_obs] local landmark                              */
+    const int32_t* pt_obs_kf;   /* HOST [n_pt_obs] keyframe slot                               */
+    const int32_t* ls_obs_lm;   /* HOST [n_ls_obs]                                             */
+    const int32_t* ls_obs_kf;   /* HOST [n_ls_obs]                                             */
+} gfpl_lba_problem;
+#define GFPL_LBA_STOP_ITERS 0   /* the loop ran out of iterations                              */
+#define GFPL_LBA_STOP_DERR  1   /* |err - err_prev| < DBL_EPSILON                              */
+#define GFPL_LBA_STOP_ERR   2   /* err < DBL_EPSILON                                           */
+#define GFPL_LBA_STOP_STEP  3   /* |DX| < DBL_EPSILON                                          */
+#define GFPL_LBA_SINGULAR   1   /* status: a pivot that is not positive and finite; that step is dropped */
+#define GFPL_LBA_HMAX_RANGE 2   /* status: a diagonal of H >= 2^31 (int Hmax overflows in the reference);
+                                   nothing is written but the result record                    */
+typedef struct gfpl_lba_result {
+    int32_t iters, stop, status, hmax;   /* iters: the reference's loop variable at exit       */
+    double  lambda, err, err_prev;
+} gfpl_lba_result;
+/* Host only, no device: GFPL_E_INVALID for a NULL problem, n_kf < 1, a negative count, no
+ * observation at all, a missing index array, landmark ids that do not start at 0, do not rise in
+ * steps of 0 or 1 or do not end at n - 1 (every landmark needs an observation), or a keyframe slot
+ * outside [-n_fix, n_kf); GFPL_E_CAPACITY for n_kf > GFPL_LBA_MAX_KFS.                         */
+int  gfpl_lba_check(const gfpl_lba_problem* p);
+/* Host only: the device workspace one problem of these counts takes and the kernel's dynamic LDS. */
+int  gfpl_lba_workspace(const gfpl_lba_counts* n, int64_t* hbm_bytes, int32_t* lds_bytes);
+/* caps: the largest counts of one problem; room for max_problems of them.  The context needs a
+ * camera (GFPL_E_STATE) and cannot be destroyed while the object lives.                        */
+int  gfpl_lba_create(gfpl_ctx* ctx, const gfpl_lba_counts* caps, int max_problems, gfpl_lba** out);
+int  gfpl_lba_destroy(gfpl_lba* lba);
+/* problems, results: HOST arrays of n.  Every problem is checked (gfpl_lba_check) before any device
+ * work; GFPL_E_CAPACITY when n or a count exceeds what the object was created for.  homog_th and the
+ * camera are the context's.  Synchronises once, for the results.                               */
+int  gfpl_lba_solve(gfpl_lba* lba, const gfpl_lba_problem* problems, int n, const gfpl_lba_params* prm,
+                    gfpl_lba_result* results);
+/* Test hook: the undamped system of the LAST iteration problem i of the last gfpl_lba_solve
+ * evaluated (iteration 0 is the pre-pass; a call with max_iters = k + 1 leaves iteration k unless
+ * it stopped earlier).  GFPL_E_STATE when that is not `iteration`.  HOST outputs, any may be NULL:
+ * U [n_kf][6][6], g [6 n_kf + 3 n_pt + 6 n_ls], V_pt [n_pt][3][3], V_ls [n_ls][6][6], W_pt
+ * [n_pt][n_kf][3][6] and W_ls [n_ls][n_kf][6][6] (landmark rows, pose columns: H.block(jdx, idx)),
+ * err (after the division).                                                                    */
+int  gfpl_lba_debug_system(gfpl_lba* lba, int i, int iteration, double* U, double* g, double* V_pt, double* V_ls,
+                           double* W_pt, double* W_ls, double* err);
+
 /* ----------------------------------------------------- state transfer ----- */
 /* Copy one sequence's frame state device -> host (synchronises).            */
 int  gfpl_read_frame(gfpl_seqbatch* sb, int which, int seq, gfpl_frame_host* out);
