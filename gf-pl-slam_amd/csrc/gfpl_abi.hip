@@ -844,6 +844,7 @@ struct Scratch {
     char* p = nullptr;
     ~Scratch() { if (p) (void)hipFree(p); }
 };
+inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 }  // namespace
 
 int gfpl_knn2_hamming_host(gfpl_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int nt, int cell, int32_t* idx,
@@ -959,6 +960,9 @@ int gfpl_kf_common_matches(gfpl_ctx* c, const gfpl_kf_view* k0, const gfpl_kf_vi
         return GFPL_E_INVALID;
     if (do_ls && (!ls_pairs || !k0->ldesc || !k1->ldesc || !k0->sP || !k0->eP || !k0->le || !k0->ls_sigma2))
         return GFPL_E_INVALID;
+    // descriptor rows are read as uint4 (include/gfpl.h: 16-byte aligned)
+    if (do_pt && (misaligned16(k0->pdesc) || misaligned16(k1->pdesc))) return GFPL_E_INVALID;
+    if (do_ls && (misaligned16(k0->ldesc) || misaligned16(k1->ldesc))) return GFPL_E_INVALID;
     if (!do_pt && !do_ls) return GFPL_OK;
     const size_t npt = do_pt ? (size_t)k0->n_pt + k1->n_pt : 0, nls = do_ls ? (size_t)k0->n_ls + k1->n_ls : 0;
     const size_t bytes = 2 * (npt + nls) * (sizeof(int32_t) + sizeof(float)) + 64;
@@ -1023,18 +1027,34 @@ int gfpl_kf_local_map_matches(gfpl_ctx* c, const gfpl_map_view* m, const gfpl_kf
     const bool do_pt = m->n_pt >= 2 && k1->n_pt >= 2, do_ls = m->n_ls >= 2 && k1->n_ls >= 2;
     if (do_pt && (!pt_pairs || !m->pdesc || !m->P || !k1->pdesc || !k1->pl)) return GFPL_E_INVALID;
     if (do_ls && (!ls_pairs || !m->ldesc || !m->L || !k1->ldesc || !k1->le)) return GFPL_E_INVALID;
+    // descriptor rows are read as uint4 (include/gfpl.h: 16-byte aligned)
+    if (do_pt && (misaligned16(m->pdesc) || misaligned16(k1->pdesc))) return GFPL_E_INVALID;
+    if (do_ls && (misaligned16(m->ldesc) || misaligned16(k1->ldesc))) return GFPL_E_INVALID;
     if (!do_pt && !do_ls) return GFPL_OK;
     const size_t n0 = (size_t)(do_pt ? m->n_pt : 0) + (do_ls ? m->n_ls : 0);
     const size_t n1 = (size_t)(do_pt ? k1->n_pt : 0) + (do_ls ? k1->n_ls : 0);
-    // loc [n0] | descs [n0][32] | idx [2 (n0 + n1)] | dist [2 (n0 + n1)] | counts [4]
-    const size_t bytes = n0 * 4 + n0 * 32 + 2 * (n0 + n1) * 8 + 64;
+    // descs [n0][32] | loc [n0] | idx [2 (n0 + n1)] | dist [2 (n0 + n1)] | counts [4], each field 256-B
+    // aligned (Carver): k_kf_map_filter writes the compacted descriptors as uint4 and the knn reads them
+    // back as uint4, and a kind's rows start at dsc + 32 * lo[kind], so every row is 32-B aligned
+    // whatever n_pt and n_ls are
+    int32_t *loc = nullptr, *idx = nullptr;
+    uint8_t* dsc = nullptr;
+    float* dist = nullptr;
+    int* cnt = nullptr;
+    Carver cv;
+    auto layout = [&]() {
+        dsc = cv.take<uint8_t>(n0 * 32);
+        loc = cv.take<int32_t>(n0);
+        idx = cv.take<int32_t>(2 * (n0 + n1));
+        dist = cv.take<float>(2 * (n0 + n1));
+        cnt = cv.take<int>(4);
+    };
+    layout();   // sizing pass (base == nullptr)
     char* scr = nullptr;
-    HIPCHK(hipMalloc(&scr, bytes));
-    int32_t* loc = reinterpret_cast<int32_t*>(scr);
-    uint8_t* dsc = reinterpret_cast<uint8_t*>(loc + n0);
-    int32_t* idx = reinterpret_cast<int32_t*>(dsc + n0 * 32);
-    float* dist = reinterpret_cast<float*>(idx + 2 * (n0 + n1));
-    int* cnt = reinterpret_cast<int*>(dist + 2 * (n0 + n1));
+    HIPCHK(hipMalloc(&scr, cv.off));
+    cv.off = 0;
+    cv.base = scr;
+    layout();
     const DevCam cam = devcam(c->cam);
     hipError_t e = hipSuccess;
     int nloc[2] = {0, 0};

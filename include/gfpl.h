@@ -627,7 +627,10 @@ int  gfpl_detector_set_rectifier(gfpl_detector* det, gfpl_rectifier* r);
  * every point array is stereo_pt[i] and row i of pdesc its left descriptor
  * (pdesc_l); likewise stereo_ls[i] / ldesc_l.  gfpl_kf_common_matches reads
  * the arrays from DEVICE memory (e.g. a gfpl_frame_host uploaded by the
- * caller, or a frame slot it copied out); T_kf_w is a host 4x4 row-major pose. */
+ * caller, or a frame slot it copied out); T_kf_w is a host 4x4 row-major pose.
+ * pdesc and ldesc must be 16-byte aligned (the kernels read a descriptor row as
+ * 16-byte vectors): gfpl_kf_common_matches and gfpl_kf_local_map_matches return
+ * GFPL_E_INVALID for a misaligned descriptor pointer of a kind they would read. */
 typedef struct gfpl_kf_view {
     int            n_pt;
     const uint8_t* pdesc;       /* [n_pt][32]                                  */
@@ -665,7 +668,8 @@ int  gfpl_kf_common_matches(gfpl_ctx* ctx, const gfpl_kf_view* kf0, const gfpl_k
  * 472-772): the map points / lines the caller keeps as local and not yet observed
  * by kf1 (`local && kf_obs_list.back() != kf1_idx`), in map order, with their
  * median descriptor (med_desc.row(0)) and 3D geometry (point3D; line3D = sP, eP).
- * Device pointers.                                                              */
+ * Device pointers; pdesc and ldesc 16-byte aligned (GFPL_E_INVALID otherwise,
+ * as for gfpl_kf_view).                                                         */
 typedef struct gfpl_map_view {
     int            n_pt;
     const uint8_t* pdesc;       /* [n_pt][32]                                  */
