@@ -161,6 +161,21 @@ struct LbaArgs {
 };
 hipError_t launch_lba(const LbaArgs& a, int n, hipStream_t s);
 
+// the landmark descriptor store (k_lm.hip); all pointers device.  The store's arrays are LmStoreMem's,
+// work / ops LmWorkMem's.
+struct LmStoreDev {
+    uint8_t* rows;
+    int32_t* count;
+    int32_t* med_idx;
+    uint8_t* med;
+    int obs_cap;
+};
+// work items [work0, work0 + n_work) through lane groups of lm_bucket_lanes(bucket)
+hipError_t launch_lm_apply(const LmStoreDev& st, const LmWork* work, const LmOpDev* ops, int work0, int n_work,
+                           int bucket, hipStream_t s);
+hipError_t launch_lm_gather(const LmStoreDev& st, const int32_t* ids, int n, uint8_t* desc_out, int32_t* med_idx_out,
+                            hipStream_t s);
+
 }  // namespace gfpl
 
 namespace gfpl {

@@ -312,4 +312,44 @@ static_assert(8 * (36 * LBA_MAX_KFS * LBA_MAX_KFS + 34 * LBA_MAX_KFS + LBA_BLOCK
                   160 * 1024 - 1024,
               "LbaLds at LBA_MAX_KFS must fit a workgroup's dynamic LDS");
 
+// ---- the landmark descriptor store (gfpl_lmstore, k_lm.hip, gfpl_lm.cpp): desc_list of every
+// landmark at a fixed stride of obs_cap rows, its length, and the row updateAverageDescDir picks
+// (index and a copy, so a gather reads one 32-byte row and never the list).  Rows at and past a
+// landmark's count keep whatever was last written there.
+constexpr int LM_MAX_OBS = 64;    // = GFPL_LM_MAX_OBS: one observation per lane of a wave
+constexpr int LM_BUCKETS = 6;     // lane groups of 2, 4, 8, 16, 32, 64 (k_lm_apply<G>)
+constexpr int LM_BLOCK = 256;     // threads of k_lm_apply and k_lm_gather
+struct LmStoreMem {
+    Carver c;
+    int lm_cap, obs_cap;
+    uint8_t* rows = c.take<uint8_t>((size_t)lm_cap * obs_cap * 32);   // [lm_cap][obs_cap][32], rows 32-B aligned
+    int32_t* count = c.take<int32_t>((size_t)lm_cap);
+    int32_t* med_idx = c.take<int32_t>((size_t)lm_cap);               // -1: no observation
+    uint8_t* med = c.take<uint8_t>((size_t)lm_cap * 32);              // [lm_cap][32] med_desc
+    size_t bytes = (c.off + 255) & ~(size_t)255;
+    LmStoreMem(char* base, int lm_cap, int obs_cap) : c{0, base}, lm_cap(lm_cap), obs_cap(obs_cap) {}
+};
+// one op as the kernel reads it: the planner's order, the source row resolved to its address
+struct LmOpDev {
+    const uint8_t* row;   // ADD: the 32-byte source row (16-B aligned)
+    int32_t kind;         // GFPL_LM_ADD / _ERASE_OBS / _FREE
+    int32_t pos;          // ERASE_OBS: the position
+};
+// one touched landmark of a call: its ops are ops[op0 .. op0 + n_ops)
+struct LmWork {
+    int32_t lm, op0, n_ops;
+    int32_t count0;       // the list's length before the call (the host mirror's; the kernel reads it from here)
+};
+// the uploaded lists of one apply (work items in bucket order, then the ops grouped by landmark),
+// laid out alike in the pinned staging and on the device so that one copy moves both
+struct LmWorkMem {
+    Carver c;
+    int max_ops;
+    LmWork* work = c.take<LmWork>((size_t)max_ops);    // at most one touched landmark per op
+    LmOpDev* ops = c.take<LmOpDev>((size_t)max_ops);
+    size_t bytes = (c.off + 255) & ~(size_t)255;
+    LmWorkMem(char* base, int max_ops) : c{0, base}, max_ops(max_ops) {}
+};
+// (k_lm_apply keeps a group's rows and distances in registers: it has no LDS layout)
+
 }  // namespace gfpl

@@ -1,0 +1,248 @@
+// gfpl_lm.cpp — host side of the landmark descriptor store (include/gfpl.h): the
+// object that owns the store's device memory and the host mirror of the counts, apply (the planner,
+// one upload of the work items and ops, one launch per lane-group bucket that has work, one
+// synchronisation), gather and read.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../include/gfpl.h"
+#include "gfpl_kernels.hpp"
+#include "gfpl_lm_plan.hpp"
+
+using namespace gfpl;
+
+struct gfpl_lmstore {
+    gfpl_ctx* ctx = nullptr;
+    int lm_cap = 0, obs_cap = 0, max_ops = 0;
+    char* base = nullptr;          // LmStoreMem, then LmWorkMem
+    size_t store_bytes = 0, work_bytes = 0;
+    char* stage = nullptr;         // pinned LmWorkMem
+    int32_t* d_ids = nullptr;      // gather's id list (grown on demand) and its pinned staging
+    int32_t* h_ids = nullptr;
+    int ids_cap = 0;
+    std::vector<int32_t> counts;   // the mirror every check runs against
+    std::vector<int32_t> slot;     // the planner's scratch, all -1 between calls
+    LmPlan plan;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the last apply's or gather's kernels (gfpl_lmstore_debug_ms)
+    bool timed = false;
+    int min_g = 0;                 // GFPL_LM_MIN_LANES as it stood when the store was created
+    bool failed = false;           // a HIP call failed inside apply: counts and rows are no longer known
+};
+
+namespace {
+
+#define LM_HIPCHK(x)                                                                    \
+    do {                                                                                \
+        hipError_t e_ = (x);                                                            \
+        if (e_ != hipSuccess) {                                                         \
+            std::fprintf(stderr, "gfpl: %s failed: %s\n", #x, hipGetErrorString(e_));   \
+            return GFPL_E_HIP;                                                          \
+        }                                                                               \
+    } while (0)
+
+hipStream_t stream_of(const gfpl_ctx* c) { return (hipStream_t)gfpl_ctx_stream(c); }
+
+LmStoreDev dev_of(const gfpl_lmstore* st) {
+    const LmStoreMem m(st->base, st->lm_cap, st->obs_cap);
+    return LmStoreDev{m.rows, m.count, m.med_idx, m.med, st->obs_cap};
+}
+
+}  // namespace
+
+extern "C" {
+
+int gfpl_lmstore_create(gfpl_ctx* c, int lm_cap, int obs_cap, int max_ops, gfpl_lmstore** out) {
+    if (!c || !out || lm_cap < 1 || obs_cap < 1 || obs_cap > GFPL_LM_MAX_OBS || max_ops < 1) return GFPL_E_INVALID;
+    LM_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
+    gfpl_lmstore* st = new gfpl_lmstore();
+    st->ctx = c;
+    st->lm_cap = lm_cap;
+    st->obs_cap = obs_cap;
+    st->max_ops = max_ops;
+    // GFPL_LM_MIN_LANES: every landmark through groups of at least so many lanes (tools/bench_lm_store.py
+    // creates a store under 64 to measure what the buckets are worth)
+    st->min_g = env_int("GFPL_LM_MIN_LANES", 0);
+    st->store_bytes = LmStoreMem(nullptr, lm_cap, obs_cap).bytes;
+    st->work_bytes = LmWorkMem(nullptr, max_ops).bytes;
+    hipStream_t s = stream_of(c);
+    bool ok = hipMalloc(&st->base, st->store_bytes + st->work_bytes) == hipSuccess &&
+              hipHostMalloc((void**)&st->stage, st->work_bytes, hipHostMallocDefault) == hipSuccess;
+    if (ok) {
+        // every landmark empty: count 0, med_idx -1, a zeroed median row
+        const LmStoreMem m(st->base, lm_cap, obs_cap);
+        ok = hipMemsetAsync(m.count, 0, (size_t)lm_cap * sizeof(int32_t), s) == hipSuccess &&
+             hipMemsetAsync(m.med_idx, 0xff, (size_t)lm_cap * sizeof(int32_t), s) == hipSuccess &&
+             hipMemsetAsync(m.med, 0, (size_t)lm_cap * 32, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            (void)hipHostFree(st->stage);
+            (void)hipFree(st->base);
+            delete st;
+            return GFPL_E_HIP;
+        }
+    } else {
+        (void)hipGetLastError();
+        if (st->base) (void)hipFree(st->base);
+        delete st;
+        return GFPL_E_NOMEM;
+    }
+    if (hipEventCreate(&st->ev0) != hipSuccess || hipEventCreate(&st->ev1) != hipSuccess) {
+        (void)hipGetLastError();
+        if (st->ev0) (void)hipEventDestroy(st->ev0);
+        (void)hipHostFree(st->stage);
+        (void)hipFree(st->base);
+        delete st;
+        return GFPL_E_HIP;
+    }
+    st->counts.assign((size_t)lm_cap, 0);
+    st->slot.assign((size_t)lm_cap, -1);
+    gfpl_ctx_attach(c);
+    *out = st;
+    return GFPL_OK;
+}
+
+int gfpl_lmstore_destroy(gfpl_lmstore* st) {
+    if (!st) return GFPL_E_INVALID;
+    (void)hipSetDevice(gfpl_ctx_device(st->ctx));
+    (void)hipStreamSynchronize(stream_of(st->ctx));
+    if (st->h_ids) (void)hipHostFree(st->h_ids);
+    if (st->d_ids) (void)hipFree(st->d_ids);
+    (void)hipEventDestroy(st->ev0);
+    (void)hipEventDestroy(st->ev1);
+    (void)hipHostFree(st->stage);
+    (void)hipFree(st->base);
+    gfpl_ctx_detach(st->ctx);
+    delete st;
+    return GFPL_OK;
+}
+
+int64_t gfpl_lmstore_bytes(const gfpl_lmstore* st) {
+    return st ? (int64_t)(st->store_bytes + st->work_bytes + (size_t)st->ids_cap * sizeof(int32_t)) : 0;
+}
+
+int gfpl_lmstore_apply(gfpl_lmstore* st, const gfpl_lm_op* ops, int n, const uint8_t* const* srcs,
+                       const int32_t* src_rows, int n_srcs) {
+    if (!st || n < 0 || (n > 0 && !ops) || n_srcs < 0 || (n_srcs > 0 && (!srcs || !src_rows))) return GFPL_E_INVALID;
+    if (st->failed) return GFPL_E_STATE;
+    if (n > st->max_ops) return GFPL_E_CAPACITY;
+    if (n == 0) return GFPL_OK;
+    const int rc = lm_plan(ops, n, st->counts.data(), st->lm_cap, st->obs_cap, src_rows, n_srcs, st->min_g, &st->plan,
+                           st->slot.data());
+    if (rc != GFPL_OK) return rc;
+    const LmPlan& pl = st->plan;
+    const LmWorkMem hm(st->stage, st->max_ops);
+    bool aligned = true;
+    for (int k = 0; k < n && aligned; ++k) {
+        const gfpl_lm_op& op = ops[pl.order[(size_t)k]];
+        LmOpDev& o = hm.ops[k];
+        o.row = nullptr;
+        o.kind = op.kind;
+        o.pos = op.arg;
+        if (op.kind == GFPL_LM_ADD) {
+            const uint8_t* p = srcs[op.src];
+            aligned = p && ((uintptr_t)p & 15) == 0;
+            if (aligned) o.row = p + 32 * (size_t)op.arg;
+        }
+    }
+    if (!aligned) {
+        for (const LmWork& w : pl.work) st->counts[(size_t)w.lm] = w.count0;   // refused: the mirror as it was
+        return GFPL_E_INVALID;
+    }
+    const int n_work = (int)pl.work.size();
+    std::memcpy(hm.work, pl.work.data(), (size_t)n_work * sizeof(LmWork));
+
+    if (hipSetDevice(gfpl_ctx_device(st->ctx)) != hipSuccess) {
+        for (const LmWork& w : pl.work) st->counts[(size_t)w.lm] = w.count0;   // nothing was enqueued
+        return GFPL_E_HIP;
+    }
+    hipStream_t s = stream_of(st->ctx);
+    const LmWorkMem dm(st->base + st->store_bytes, st->max_ops);
+    const LmStoreDev sd = dev_of(st);
+    hipError_t e = hipMemcpyAsync(dm.work, hm.work, (size_t)n_work * sizeof(LmWork), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(dm.ops, hm.ops, (size_t)n * sizeof(LmOpDev), hipMemcpyHostToDevice, s);
+    st->timed = false;
+    if (e == hipSuccess) e = hipEventRecord(st->ev0, s);
+    for (int b = 0; b < LM_BUCKETS && e == hipSuccess; ++b)
+        e = launch_lm_apply(sd, dm.work, dm.ops, pl.bucket_start[b], pl.bucket_start[b + 1] - pl.bucket_start[b], b, s);
+    if (e == hipSuccess) e = hipEventRecord(st->ev1, s);
+    const hipError_t es = hipStreamSynchronize(s);   // also on an error path: the staging is still in use
+    st->timed = e == hipSuccess && es == hipSuccess;
+    if (e != hipSuccess || es != hipSuccess) {
+        // some of the launches may have run: neither the mirror's counts nor the ones before the call
+        // describe the device any more, so the store refuses further use
+        std::fprintf(stderr, "gfpl: lmstore_apply failed: %s\n", hipGetErrorString(e != hipSuccess ? e : es));
+        st->failed = true;
+        return GFPL_E_HIP;
+    }
+    return GFPL_OK;
+}
+
+int gfpl_lmstore_gather(gfpl_lmstore* st, const int32_t* lm_ids, int n, uint8_t* desc_out, int32_t* med_idx_out) {
+    if (!st || n < 0 || (n > 0 && (!lm_ids || !desc_out))) return GFPL_E_INVALID;
+    if (st->failed) return GFPL_E_STATE;
+    if (n == 0) return GFPL_OK;
+    if ((uintptr_t)desc_out & 15) return GFPL_E_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (lm_ids[i] < 0 || lm_ids[i] >= st->lm_cap || st->counts[(size_t)lm_ids[i]] == 0) return GFPL_E_INVALID;
+    LM_HIPCHK(hipSetDevice(gfpl_ctx_device(st->ctx)));
+    hipStream_t s = stream_of(st->ctx);
+    if (n > st->ids_cap) {
+        if (st->h_ids) (void)hipHostFree(st->h_ids);
+        if (st->d_ids) (void)hipFree(st->d_ids);
+        st->h_ids = nullptr;
+        st->d_ids = nullptr;
+        st->ids_cap = 0;
+        const bool ok = hipMalloc(&st->d_ids, (size_t)n * sizeof(int32_t)) == hipSuccess &&
+                        hipHostMalloc((void**)&st->h_ids, (size_t)n * sizeof(int32_t), hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            if (st->d_ids) (void)hipFree(st->d_ids);
+            st->d_ids = nullptr;
+            return GFPL_E_NOMEM;
+        }
+        st->ids_cap = n;
+    }
+    std::memcpy(st->h_ids, lm_ids, (size_t)n * sizeof(int32_t));
+    hipError_t e = hipMemcpyAsync(st->d_ids, st->h_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s);
+    st->timed = false;
+    if (e == hipSuccess) e = hipEventRecord(st->ev0, s);
+    if (e == hipSuccess) e = launch_lm_gather(dev_of(st), st->d_ids, n, desc_out, med_idx_out, s);
+    if (e == hipSuccess) e = hipEventRecord(st->ev1, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    st->timed = e == hipSuccess && es == hipSuccess;
+    if (e != hipSuccess || es != hipSuccess) {
+        std::fprintf(stderr, "gfpl: lmstore_gather failed: %s\n", hipGetErrorString(e != hipSuccess ? e : es));
+        return GFPL_E_HIP;
+    }
+    return GFPL_OK;
+}
+
+int gfpl_lmstore_read(gfpl_lmstore* st, int lm, int32_t* count, int32_t* med_idx, uint8_t* desc_list, uint8_t* med_desc) {
+    if (!st || lm < 0 || lm >= st->lm_cap) return GFPL_E_INVALID;
+    if (st->failed) return GFPL_E_STATE;
+    LM_HIPCHK(hipSetDevice(gfpl_ctx_device(st->ctx)));
+    hipStream_t s = stream_of(st->ctx);
+    const LmStoreDev sd = dev_of(st);
+    hipError_t e = hipSuccess;
+    if (count) e = hipMemcpyAsync(count, sd.count + lm, sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && med_idx) e = hipMemcpyAsync(med_idx, sd.med_idx + lm, sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && desc_list)
+        e = hipMemcpyAsync(desc_list, sd.rows + (size_t)lm * st->obs_cap * 32, (size_t)st->obs_cap * 32,
+                           hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && med_desc) e = hipMemcpyAsync(med_desc, sd.med + (size_t)lm * 32, 32, hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e != hipSuccess || es != hipSuccess) return GFPL_E_HIP;
+    return GFPL_OK;
+}
+
+int gfpl_lmstore_debug_ms(gfpl_lmstore* st, float* ms) {
+    if (!st || !ms) return GFPL_E_INVALID;
+    if (!st->timed) return GFPL_E_STATE;
+    LM_HIPCHK(hipEventElapsedTime(ms, st->ev0, st->ev1));
+    return GFPL_OK;
+}
+
+}  // extern "C"

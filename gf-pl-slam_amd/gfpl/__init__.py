@@ -626,6 +626,14 @@ def hiplib() -> C.CDLL:
             "gfpl_lba_destroy": ([P], C.c_int),
             "gfpl_lba_solve": ([P, P, C.c_int, P, P], C.c_int),
             "gfpl_lba_debug_system": ([P, C.c_int, C.c_int, P, P, P, P, P, P, P], C.c_int),
+            "gfpl_lmstore_create": ([P, C.c_int, C.c_int, C.c_int, C.POINTER(P)], C.c_int),
+            "gfpl_lmstore_destroy": ([P], C.c_int),
+            "gfpl_lmstore_bytes": ([P], C.c_int64),
+            "gfpl_lm_ops_check": ([P, C.c_int, P, C.c_int, C.c_int, P, C.c_int], C.c_int),
+            "gfpl_lmstore_apply": ([P, P, C.c_int, P, P, C.c_int], C.c_int),
+            "gfpl_lmstore_gather": ([P, P, C.c_int, P, P], C.c_int),
+            "gfpl_lmstore_read": ([P, C.c_int, P, P, P, P], C.c_int),
+            "gfpl_lmstore_debug_ms": ([P, P], C.c_int),
         }
         for n, (a, r) in sigs.items():
             try:
@@ -1272,6 +1280,97 @@ class LbaSolver:
     def close(self):
         if getattr(self, "h", None):
             check(self.L.gfpl_lba_destroy(self.h), "lba_destroy")
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+LM_MAX_OBS = 64
+LM_ADD, LM_ERASE_OBS, LM_FREE = 0, 1, 2
+
+
+def _lm_ops(ops) -> np.ndarray:
+    """Ops as an int32 [n][4] array of gfpl_lm_op rows (lm, kind, arg, src)."""
+    a = np.ascontiguousarray(ops, np.int32)
+    return a.reshape(-1, 4) if a.size else np.zeros((0, 4), np.int32)
+
+
+def lm_ops_check(ops, counts, obs_cap: int, src_rows):
+    """gfpl_lm_ops_check (host only): (return code, counts after).  counts [lm_cap] before the ops;
+    src_rows: the rows of every source.  A refused list returns the counts unchanged."""
+    o = _lm_ops(ops)
+    cnt = np.array(counts, np.int32)
+    rows = np.ascontiguousarray(src_rows, np.int32).reshape(-1)
+    rc = hiplib().gfpl_lm_ops_check(_ptr(o), len(o), _ptr(cnt), len(cnt), int(obs_cap),
+                                    _ptr(rows) if len(rows) else 0, len(rows))
+    return rc, cnt
+
+
+class LandmarkStore:
+    """gfpl_lmstore: desc_list and med_desc of lm_cap MapPoints or MapLines on the device
+    (src/mapFeatures.cpp:28-92).  apply() takes ops [n][4] (lm, kind, arg, src) and the source
+    descriptor arrays (torch device tensors [rows][32] uint8); gather() compacts the median rows of
+    an id list into a device tensor; read() copies one landmark to the host.  The context cannot be
+    closed while the store is open."""
+
+    def __init__(self, ctx: "Context", lm_cap: int, obs_cap: int, max_ops: int):
+        self.ctx, self.L = ctx, ctx.L
+        self.lm_cap, self.obs_cap, self.max_ops = int(lm_cap), int(obs_cap), int(max_ops)
+        self.h = C.c_void_p()
+        check(self.L.gfpl_lmstore_create(ctx.h, self.lm_cap, self.obs_cap, self.max_ops, C.byref(self.h)), "lmstore_create")
+
+    def apply_rc(self, ops, srcs, src_rows=None, src_ptrs=None) -> int:
+        """gfpl_lmstore_apply's return code.  src_ptrs overrides the sources' device addresses (the
+        tests pass a misaligned one)."""
+        import torch
+        o = _lm_ops(ops)
+        srcs = list(srcs)
+        rows = np.array([int(s.shape[0]) for s in srcs] if src_rows is None else src_rows, np.int32)
+        ptrs = (C.c_void_p * max(len(srcs), 1))(*([_ptr(s) for s in srcs] if src_ptrs is None else src_ptrs))
+        torch.cuda.synchronize()
+        return self.L.gfpl_lmstore_apply(self.h, _ptr(o), len(o), ptrs if len(srcs) else None,
+                                         _ptr(rows) if len(srcs) else 0, len(srcs))
+
+    def apply(self, ops, srcs, src_rows=None) -> None:
+        check(self.apply_rc(ops, srcs, src_rows), "lmstore_apply")
+
+    def gather(self, ids, with_idx: bool = False):
+        """Device tensor [n][32] of the ids' median rows (a MapView's pdesc / ldesc); with_idx: also
+        their med_idx [n]."""
+        import torch
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        dev = torch.device("cuda", self.ctx.device)
+        out = torch.zeros((max(len(ids), 1), 32), dtype=torch.uint8, device=dev)
+        idx = torch.full((max(len(ids), 1),), -2, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        check(self.L.gfpl_lmstore_gather(self.h, _ptr(ids), len(ids), _ptr(out), _ptr(idx)), "lmstore_gather")
+        return (out[: len(ids)], idx[: len(ids)]) if with_idx else out[: len(ids)]
+
+    def read(self, lm: int) -> dict:
+        """count, med_idx, desc_list [obs_cap][32] (rows at and past count are whatever the store
+        last held there) and med_desc [32] of one landmark."""
+        cnt, mi = C.c_int32(0), C.c_int32(0)
+        rows = np.zeros((self.obs_cap, 32), np.uint8)
+        med = np.zeros(32, np.uint8)
+        check(self.L.gfpl_lmstore_read(self.h, int(lm), C.byref(cnt), C.byref(mi), _ptr(rows), _ptr(med)), "lmstore_read")
+        return dict(count=cnt.value, med_idx=mi.value, desc_list=rows, med_desc=med)
+
+    def nbytes(self) -> int:
+        return int(self.L.gfpl_lmstore_bytes(self.h))
+
+    def last_device_ms(self) -> float:
+        """gfpl_lmstore_debug_ms: device time of the last apply's or gather's kernels."""
+        ms = C.c_float(0.0)
+        check(self.L.gfpl_lmstore_debug_ms(self.h, C.byref(ms)), "lmstore_debug_ms")
+        return float(ms.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            check(self.L.gfpl_lmstore_destroy(self.h), "lmstore_destroy")
             self.h = None
 
     def __del__(self):

@@ -731,6 +731,63 @@ int  gfpl_kf_loop_closure(gfpl_ctx* ctx, const gfpl_kf_view* kf0, const gfpl_kf_
                           int32_t* pt_pairs, uint8_t* pt_inlier, int32_t* ls_pairs, uint8_t* ls_inlier,
                           gfpl_loop_result* out);
 
+/* ------------------------------------------- landmark descriptor store ---- */
+/* MapPoint / MapLine::desc_list and med_desc on the device (src/mapFeatures.cpp:28-92, 96-162;
+ * k_lm.hip, DESIGN.md §4i, ledger LM1-LM7).  A store holds, for lm_cap landmarks, up to obs_cap
+ * 32-byte NORM_HAMMING descriptors each, and for every landmark the observation that
+ * updateAverageDescDir picks: all pairwise Hamming distances, the element 1 + (n - 1) / 2 of every
+ * sorted row (the row includes the landmark's own 0), the first row of least such median.  One
+ * store serves points or lines; a caller keeps two.  obs_list, kf_obs_list, dir_list, sigma_list,
+ * the 3D geometry and med_obs_dir stay with the caller.                                          */
+#define GFPL_LM_MAX_OBS 64          /* observations per landmark the store can hold */
+#define GFPL_LM_ADD       0         /* desc_list.push_back(row arg of srcs[src]); a landmark with no observation is created */
+#define GFPL_LM_ERASE_OBS 1         /* desc_list.erase(begin() + arg): later observations move down by one */
+#define GFPL_LM_FREE      2         /* map_points[lm] = NULL: the landmark holds nothing afterwards */
+typedef struct gfpl_lm_op { int32_t lm, kind, arg, src; } gfpl_lm_op;   /* src is read for GFPL_LM_ADD only */
+typedef struct gfpl_lmstore gfpl_lmstore;
+
+/* lm_cap >= 1 landmarks (lm_cap * obs_cap * 32 bytes of rows), at most max_ops >= 1 ops per apply.
+ * Every landmark starts empty.  The context cannot be destroyed while the store lives.          */
+int  gfpl_lmstore_create(gfpl_ctx* ctx, int lm_cap, int obs_cap /*1..GFPL_LM_MAX_OBS*/, int max_ops, gfpl_lmstore** out);
+int  gfpl_lmstore_destroy(gfpl_lmstore* st);
+int64_t gfpl_lmstore_bytes(const gfpl_lmstore* st);   /* device bytes: the store and the uploaded lists */
+/* Host only, no device: simulates the counts of an op list.  counts [lm_cap]: in, every landmark's
+ * count before; out, after (unchanged when the list is refused).  The ops are checked in array
+ * order and the first that fails decides: GFPL_E_INVALID for a NULL pointer, n < 0, lm_cap < 1,
+ * obs_cap outside 1..GFPL_LM_MAX_OBS, a count outside [0, obs_cap], lm outside [0, lm_cap), an
+ * unknown kind, an ADD whose src is outside [0, n_srcs) or whose row is outside [0, src_rows[src]),
+ * an ERASE_OBS position outside the list as it stands at that op; GFPL_E_CAPACITY for an ADD to a
+ * list of obs_cap.  FREE of an empty landmark is allowed.  n = 0 is GFPL_OK.                   */
+int  gfpl_lm_ops_check(const gfpl_lm_op* ops, int n, int32_t* counts /*[lm_cap] in: before, out: after*/,
+                       int lm_cap, int obs_cap, const int32_t* src_rows, int n_srcs);
+/* Applies the ops: those of one landmark in array order, landmarks independently of each other.
+ * Afterwards every landmark an op named has the med_idx / med_desc of updateAverageDescDir over its
+ * final list (the reference recomputes after every append; nothing reads the value in between); an
+ * empty list has count 0, med_idx -1 and a zeroed median row.  Runs gfpl_lm_ops_check against the
+ * store's counts before any device work, with the same codes; GFPL_E_CAPACITY also for n > max_ops,
+ * GFPL_E_INVALID also for an ADD from a NULL or misaligned srcs[src].  A refused call changes
+ * nothing.  ADD rows are read during the call.  Synchronises once.  GFPL_E_HIP from a copy, launch
+ * or synchronisation of the call leaves the store's contents unknown: apply, gather and read return
+ * GFPL_E_STATE from then on and the store can only be destroyed.                                */
+int  gfpl_lmstore_apply(gfpl_lmstore* st, const gfpl_lm_op* ops /*HOST*/, int n,
+                        const uint8_t* const* srcs /*HOST array of DEVICE [rows][32], 16-B aligned*/,
+                        const int32_t* src_rows, int n_srcs);
+/* The median rows of lm_ids, compacted in the order given (ids may repeat): row i of desc_out is
+ * med_desc of lm_ids[i], med_idx_out[i] its index in desc_list.  The selection `local &&
+ * kf_obs_list.back() != kf1_idx` stays the caller's; desc_out is a gfpl_map_view's pdesc / ldesc.
+ * GFPL_E_INVALID, and nothing written, for an id outside [0, lm_cap) or of a landmark without an
+ * observation, or a misaligned desc_out.  Synchronises once.                                    */
+int  gfpl_lmstore_gather(gfpl_lmstore* st, const int32_t* lm_ids /*HOST [n]*/, int n,
+                         uint8_t* desc_out /*DEVICE [n][32], 16-B aligned*/, int32_t* med_idx_out /*DEVICE [n] or NULL*/);
+/* One landmark to the host (any output may be NULL).  desc_list receives all obs_cap rows as the
+ * store holds them: rows [0, count) are the list, the others whatever was last written there.
+ * Synchronises once.                                                                            */
+int  gfpl_lmstore_read(gfpl_lmstore* st, int lm, int32_t* count, int32_t* med_idx,
+                       uint8_t* desc_list /*HOST [obs_cap][32] or NULL*/, uint8_t* med_desc /*HOST [32] or NULL*/);
+/* Instrumentation (tools/bench_lm_store.py): device milliseconds between the first and the last
+ * kernel of the store's last apply or gather that launched any; GFPL_E_STATE when there is none. */
+int  gfpl_lmstore_debug_ms(gfpl_lmstore* st, float* ms);
+
 /* ------------------------------------- loop-closure candidate search ----- */
 /* DBoW2 as MapHandler uses it (insertKFBowVectorP / L / PL, src/mapHandler.cpp:2865-3000, and
  * lookForLoopCandidates, :3002-3076): TemplatedVocabulary<FORB>::transform and L1Scoring::score
