@@ -176,6 +176,25 @@ hipError_t launch_lm_apply(const LmStoreDev& st, const LmWork* work, const LmOpD
 hipError_t launch_lm_gather(const LmStoreDev& st, const int32_t* ids, int n, uint8_t* desc_out, int32_t* med_idx_out,
                             hipStream_t s);
 
+// the loop-closure pose graph (k_pgo.hip): one problem; all pointers device.  The index arrays are
+// PgoIdx's uploaded copies of the planner's lists, m the problem's workspace (PgoMem).
+struct PgoProb {
+    gfpl_pgo_counts n;            // n_pt / n_ls: point / line jobs
+    int32_t kf_curr, pad;
+    double *T_kf, *x_kf, *pt, *ls, *pt_dir, *ls_dir;
+    const int32_t *vert, *free_vert, *edge, *inc_start, *inc, *env_first, *env_off, *reach, *lc, *alive, *jobs;
+    const double* lc_pose;
+    PgoPtrs m;
+};
+struct PgoArgs {
+    gfpl_pgo_graph_params prm;
+    const PgoProb* probs;         // [n]
+    gfpl_pgo_result* out;         // [n]
+};
+hipError_t launch_pgo(const PgoArgs& a, int n, hipStream_t s);
+// the map correction of n problems whose largest job count is max_jobs (> 0)
+hipError_t launch_pgo_correct(const PgoProb* probs, int n, int max_jobs, hipStream_t s);
+
 }  // namespace gfpl
 
 namespace gfpl {

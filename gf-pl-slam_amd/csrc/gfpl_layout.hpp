@@ -352,4 +352,71 @@ struct LmWorkMem {
 };
 // (k_lm_apply keeps a group's rows and distances in registers: it has no LDS layout)
 
+// ---- the loop-closure pose graph (k_pgo.hip, gfpl_pgo.cpp, gfpl_pgo_plan.cpp).  Vertices are the
+// keyframes of kf_list in order, free vertices (not fixed) are numbered in that order too, and the
+// free system's row r (a 6 x 6 block row) is stored from its first block column f(r) to r.
+constexpr int PGO_BLOCK = 256;    // threads of k_pgo = edges per pass = entries of the chi2 staging
+constexpr int PGO_ROW = 78;       // doubles per edge row: e[6], J_i[6][6], J_j[6][6]
+constexpr int PGO_RED = 78;       // reduction lanes per free vertex: 36 diagonal, 6 gradient, 36 off-diagonal
+constexpr int PGO_PANEL = 16;     // block columns of the pivot row staged in LDS at a time
+constexpr int PGO_VERT_LC_J = 2, PGO_VERT_FIXED = 1, PGO_VERT_LC_I = 4;
+// the index arrays of one problem, laid out alike in the pinned staging and on the device so that
+// one copy moves them (every count is the problem's own; the arrays are the planner's, PgoPlan)
+struct PgoIdx {
+    Carver c;
+    int nkf, nlc, nvert, nfree, nedge, njobs;
+    int32_t* vert = c.take<int32_t>((size_t)nvert * 4);       // keyframe, flags, lc_id, free index
+    int32_t* free_vert = c.take<int32_t>((size_t)nfree);      // vertex of free index r
+    int32_t* edge = c.take<int32_t>((size_t)nedge * 4);       // vertex i, vertex j, loop entry or -1, 0
+    int32_t* inc_start = c.take<int32_t>((size_t)nfree + 1);  // incident edges of free vertex r, edge-list order
+    int32_t* inc = c.take<int32_t>((size_t)nedge * 2);
+    int32_t* env_first = c.take<int32_t>((size_t)nfree);      // f(r)
+    int32_t* env_off = c.take<int32_t>((size_t)nfree + 1);    // first block of row r in the envelope arrays
+    int32_t* reach = c.take<int32_t>((size_t)nfree);          // the last row whose envelope holds column c
+    int32_t* lc = c.take<int32_t>((size_t)nlc * 3);
+    int32_t* alive = c.take<int32_t>((size_t)nkf);
+    int32_t* jobs = c.take<int32_t>((size_t)njobs * 4);       // landmark, keyframe, first dir row, dir rows; points first
+    double* lc_pose = c.take<double>((size_t)nlc * 6);
+    size_t bytes = (c.off + 255) & ~(size_t)255;
+    PgoIdx(char* base, int nkf, int nlc, int nvert, int nfree, int nedge, int njobs)
+        : c{0, base}, nkf(nkf), nlc(nlc), nvert(nvert), nfree(nfree), nedge(nedge), njobs(njobs) {}
+};
+struct PgoPtrs {
+    double *X, *Xt, *X0;          // [n_vert][16] poses, trial poses, start poses
+    double* Z;                    // [n_edge][16] measurements
+    double* rows;                 // [n_edge][PGO_ROW]
+    double* esq;                  // [n_edge] e . e of the last evaluation
+    double *diag, *b;             // [n_free][36], [6 n_free]: undamped diagonal blocks, J^T e
+    double *H, *L;                // [env_blocks][36]: undamped envelope (diagonal places zero), the factor of H + lambda I
+    double *D, *y;                // [6 n_free] pivots, right-hand side / step
+    double* corr;                 // [n_kf][16] Tkfw_corr of every keyframe the write-back moved
+    int32_t* moved;               // [n_kf] 1: corr is set
+    int32_t* state;               // [8]: 0 linearisations so far
+};
+struct PgoMem {
+    Carver c;
+    int nkf, nvert, nfree, nedge, nenv;
+    PgoPtrs p{c.take<double>((size_t)nvert * 16), c.take<double>((size_t)nvert * 16), c.take<double>((size_t)nvert * 16),
+              c.take<double>((size_t)nedge * 16), c.take<double>((size_t)nedge * PGO_ROW), c.take<double>((size_t)nedge),
+              c.take<double>((size_t)nfree * 36), c.take<double>((size_t)nfree * 6),
+              c.take<double>((size_t)nenv * 36), c.take<double>((size_t)nenv * 36),
+              c.take<double>((size_t)nfree * 6), c.take<double>((size_t)nfree * 6),
+              c.take<double>((size_t)nkf * 16), c.take<int32_t>((size_t)nkf), c.take<int32_t>(8)};
+    size_t bytes = (c.off + 255) & ~(size_t)255;
+    PgoMem(char* base, int nkf, int nvert, int nfree, int nedge, int nenv)
+        : c{0, base}, nkf(nkf), nvert(nvert), nfree(nfree), nedge(nedge), nenv(nenv) {}
+};
+// ---- k_pgo: the staged piece of the pivot row (L[k][m] and D[m] of PGO_PANEL block columns), the
+// chi2 staging and the loop's state; the same for every problem size
+struct PgoLds {
+    LdsCarver c;
+    double* pk = c.take<double>(6 * PGO_PANEL);
+    double* pd = c.take<double>(6 * PGO_PANEL);
+    double* red = c.take<double>(PGO_BLOCK);
+    double* sd = c.take<double>(16);     // lambda, nu, chi2, chi2 of the trial, |delta|_inf, scale, chi2_0, chi2 before the step
+    int* si = c.take<int>(16);           // iters, stop, status, rejects, done, singular, accept, rejects of the iteration
+    int bytes = c.off;
+    GFPL_HD explicit PgoLds(unsigned char* smem) : c(smem) {}
+};
+
 }  // namespace gfpl

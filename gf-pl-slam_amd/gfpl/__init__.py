@@ -634,6 +634,14 @@ def hiplib() -> C.CDLL:
             "gfpl_lmstore_gather": ([P, P, C.c_int, P, P], C.c_int),
             "gfpl_lmstore_read": ([P, C.c_int, P, P, P, P], C.c_int),
             "gfpl_lmstore_debug_ms": ([P, P], C.c_int),
+            "gfpl_default_pgo_params": ([P], None),
+            "gfpl_pgo_check": ([P, P, P], C.c_int),
+            "gfpl_pgo_workspace": ([P, P, P], C.c_int),
+            "gfpl_pgo_create": ([P, P, C.c_int, C.POINTER(P)], C.c_int),
+            "gfpl_pgo_destroy": ([P], C.c_int),
+            "gfpl_pgo_solve": ([P, P, C.c_int, P, P], C.c_int),
+            "gfpl_pgo_debug_system": ([P, C.c_int, P, P, P, P, P, P, P, P, P], C.c_int),
+            "gfpl_pgo_debug_ms": ([P, P, P], C.c_int),
         }
         for n, (a, r) in sigs.items():
             try:
@@ -1181,6 +1189,36 @@ class Context:
         prm.max_iters = iteration + 1
         return self._lba_run([problem], prm, debug=(0, iteration))[1]
 
+    def _pgo_run(self, problems, prm, debug=None):
+        counts = []
+        for p in problems:   # the host rules first: nothing is allocated for a refused problem
+            rc, c = p.check(prm)
+            if rc != 0:
+                raise GfplError(rc, "pgo_check")
+            counts.append(c)
+        solver = PoseGraph(self, counts, max(len(problems), 1))
+        try:
+            return solver.solve(problems, prm, debug)
+        finally:
+            solver.close()
+
+    def loopClosureOptimization(self, problems, params: Optional["PoseGraphParams"] = None):
+        """MapHandler::loopClosureOptimizationCovGraphG2O / EssGraphG2O (src/mapHandler.cpp:4187-4419,
+        :3950-4184; params.variant) for a batch of PoseGraphProblem in one call (a single problem may be
+        passed): the pose graph, its Levenberg-Marquardt solve and the correction of every keyframe
+        pose and owned landmark, all on the device.  Per problem a dict (see PoseGraph.solve)."""
+        single = isinstance(problems, PoseGraphProblem)
+        res = self._pgo_run([problems] if single else list(problems), params if params is not None else PoseGraphParams.default())
+        return res[0] if single else res
+
+    def pgoDebugSystem(self, problem: "PoseGraphProblem", params: Optional["PoseGraphParams"] = None):
+        """Test hook (gfpl_pgo_debug_system): iteration 0's chi2, b, the diagonal and envelope blocks (and
+        H, the dense lower triangle they make), the vertex and edge lists, Z and the start poses X0,
+        from a solve of one iteration.  Returns (that solve's results, the system)."""
+        prm = PoseGraphParams.default() if params is None else PoseGraphParams.from_buffer_copy(params)
+        prm.max_iters = 1
+        return self._pgo_run([problem], prm, debug=0)
+
     def close(self):
         """gfpl_destroy.  Refused (GfplError, the handle kept) while a StereoFrameHandler
         created on this context is still open: close those first."""
@@ -1280,6 +1318,219 @@ class LbaSolver:
     def close(self):
         if getattr(self, "h", None):
             check(self.L.gfpl_lba_destroy(self.h), "lba_destroy")
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ------------------------------------------------- loop-closure pose graph --
+PGO_COV, PGO_ESS = 0, 1
+PGO_STOP_ITERS, PGO_STOP_STEP, PGO_STOP_DCHI2, PGO_STOP_REJECT, PGO_STOP_NOFREE = 0, 1, 2, 3, 4
+PGO_SINGULAR = 1
+PGO_VERT_FIXED, PGO_VERT_LC_J, PGO_VERT_LC_I = 1, 2, 4
+PGO_BLOCK, PGO_RED, PGO_PANEL = 256, 78, 16   # k_pgo's threads, reduction lanes per free vertex, LDS panel (gfpl_layout.hpp)
+PGO_GUARD = 32                                # sentinel doubles on either side of every device array of a solve
+
+
+class PoseGraphParams(C.Structure):
+    """gfpl_pgo_graph_params: Config::minLMEssGraph / minLMCovGraph (src/config.cpp:50-51), the variant
+    (PGO_COV / PGO_ESS) and the iteration (optimize(100), setUserLambdaInit(1e-10), 10 retries)."""
+    _fields_ = [("min_lm_ess_graph", C.c_int32), ("min_lm_cov_graph", C.c_int32), ("variant", C.c_int32),
+                ("max_iters", C.c_int32), ("max_rejects", C.c_int32), ("pad", C.c_int32), ("lambda_init", C.c_double)]
+
+    @classmethod
+    def default(cls, **over) -> "PoseGraphParams":
+        p = cls()
+        hiplib().gfpl_default_pgo_params(C.byref(p))
+        for k, v in over.items():
+            setattr(p, k, v)
+        return p
+
+
+class PgoCounts(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_kf", "n_lc", "n_vert", "n_free", "n_edge", "env_blocks", "n_pt", "n_ls")]
+
+
+class PgoProblemStruct(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_kf", "n_lc", "n_pt", "n_ls")] + [(k, _vp) for k in (
+        "alive", "full_graph", "lc", "lc_pose", "T_kf", "x_kf", "pt", "ls", "pt_dir", "ls_dir", "pt_kf_start", "pt_kf_idx",
+        "ls_kf_start", "ls_kf_idx", "pt_dir_off", "ls_dir_off", "pt_freed", "ls_freed")]
+
+
+class PgoResult(C.Structure):
+    """gfpl_pgo_result: iters accepted iterations; stop PGO_STOP_*; status bit PGO_SINGULAR; rejects the
+    rejected trials; the graph's counts; lambda, chi2_0 and chi2 at exit."""
+    _fields_ = [("iters", C.c_int32), ("stop", C.c_int32), ("status", C.c_int32), ("rejects", C.c_int32),
+                ("n_vert", C.c_int32), ("n_free", C.c_int32), ("n_edge", C.c_int32), ("kf_curr", C.c_int32),
+                ("lambda_", C.c_double), ("chi2_0", C.c_double), ("chi2", C.c_double)]
+
+
+def _csr(lists, n_kf):
+    start = np.zeros(n_kf + 1, np.int32)
+    for i in range(n_kf):
+        start[i + 1] = start[i] + len(lists[i])
+    idx = np.array([j for l in lists for j in l], np.int32).reshape(-1)
+    return start, idx
+
+
+class PoseGraphProblem:
+    """One loop-closure optimisation (gfpl_pgo_problem) from numpy arrays: alive [n_kf], full_graph
+    [n_kf][n_kf], lc [n_lc][3] (kf_prev, kf_curr, flag) with lc_pose [n_lc][6], T_kf [n_kf][4][4]; the
+    map: pt [n_pt][3], ls [n_ls][6], pt_own / ls_own (per keyframe the list of landmark ids it owns,
+    an id < 0 a freed landmark), optional pt_dirs / ls_dirs (per landmark an [n][3] array: dir_list;
+    None: the caller does not keep them on the device) and pt_freed / ls_freed marks."""
+
+    def __init__(self, alive, full_graph, lc, lc_pose, T_kf, pt=None, ls=None, pt_own=None, ls_own=None,
+                 pt_dirs=None, ls_dirs=None, pt_freed=None, ls_freed=None):
+        a = self.a = {}
+        a["alive"] = np.ascontiguousarray(np.asarray(alive).astype(np.uint8).reshape(-1))
+        n_kf = self.n_kf = len(a["alive"])
+        a["full_graph"] = np.ascontiguousarray(np.asarray(full_graph, np.int32).reshape(n_kf, n_kf))
+        a["lc"] = np.array(lc, np.int32).reshape(-1, 3)            # (copies: the caller's lists stay the caller's)
+        a["lc_pose"] = np.array(lc_pose, np.float64).reshape(-1, 6)
+        a["T_kf"] = np.ascontiguousarray(np.asarray(T_kf, np.float64).reshape(-1, 16))
+        a["pt"] = np.ascontiguousarray(np.asarray(pt if pt is not None else np.zeros((0, 3)), np.float64).reshape(-1, 3))
+        a["ls"] = np.ascontiguousarray(np.asarray(ls if ls is not None else np.zeros((0, 6)), np.float64).reshape(-1, 6))
+        for k, own, dirs, freed, n in (("pt", pt_own, pt_dirs, pt_freed, len(a["pt"])), ("ls", ls_own, ls_dirs, ls_freed, len(a["ls"]))):
+            own = own if own is not None else [[] for _ in range(n_kf)]
+            a[k + "_kf_start"], a[k + "_kf_idx"] = _csr(own, n_kf)
+            if dirs is not None:
+                off = np.zeros(n + 1, np.int32)
+                for j in range(n):
+                    off[j + 1] = off[j] + len(dirs[j])
+                a[k + "_dir_off"] = off
+                rows = [np.asarray(d, np.float64).reshape(-1, 3) for d in dirs]
+                a[k + "_dir"] = np.ascontiguousarray(np.concatenate(rows + [np.zeros((0, 3))]))
+            else:
+                a[k + "_dir_off"] = a[k + "_dir"] = None
+            a[k + "_freed"] = None if freed is None else np.ascontiguousarray(np.asarray(freed).astype(np.uint8).reshape(-1))
+
+    DEVICE = ("T_kf", "x_kf", "pt", "ls", "pt_dir", "ls_dir")
+
+    def struct(self, dev=None) -> PgoProblemStruct:
+        """The C record: the index arrays on the host; the map's doubles on the host (dev=None, for
+        check()) or the device tensors of `dev` (a dict name -> tensor)."""
+        a, s = self.a, PgoProblemStruct()
+        s.n_kf, s.n_lc, s.n_pt, s.n_ls = self.n_kf, len(a["lc"]), len(a["pt"]), len(a["ls"])
+        for k in ("alive", "full_graph", "lc", "lc_pose", "pt_kf_start", "pt_kf_idx", "ls_kf_start", "ls_kf_idx",
+                  "pt_dir_off", "ls_dir_off", "pt_freed", "ls_freed"):
+            setattr(s, k, _ptr(a[k]) if a[k] is not None and a[k].size else None)
+        if dev is None:
+            self._x = np.zeros((self.n_kf, 6))
+            dev = dict(a, x_kf=self._x)
+        for k in self.DEVICE:
+            v = dev.get(k)
+            setattr(s, k, _ptr(v) if v is not None and (k.endswith("_dir") or len(v)) else None)
+        return s
+
+    def check(self, params: Optional[PoseGraphParams] = None):
+        """gfpl_pgo_check (host only): (return code, PgoCounts of the graph)."""
+        prm = params if params is not None else PoseGraphParams.default()
+        cnt = PgoCounts()
+        rc = hiplib().gfpl_pgo_check(C.byref(self.struct()), C.byref(prm), C.byref(cnt))
+        return rc, cnt
+
+
+def pgoWorkspace(counts: PgoCounts):
+    """gfpl_pgo_workspace: (return code, hbm_bytes, lds_bytes) for one problem of these counts."""
+    hbm, lds = C.c_int64(0), C.c_int32(0)
+    rc = hiplib().gfpl_pgo_workspace(C.byref(counts), C.byref(hbm), C.byref(lds))
+    return rc, hbm.value, lds.value
+
+
+class PoseGraph:
+    """gfpl_pgo: the device workspace of up to max_problems loop-closure optimisations whose counts
+    stay within caps (a PgoCounts, or the largest of a list of them); solve() may be called any number
+    of times.  The context cannot be closed while the object is open."""
+
+    def __init__(self, ctx: "Context", caps, max_problems: int):
+        self.ctx, self.L = ctx, ctx.L
+        if not isinstance(caps, PgoCounts):
+            caps = PgoCounts(*[max([getattr(c, f) for c in caps] + [1 if f in ("n_kf", "n_lc", "n_edge") else 0])
+                               for f, _ in PgoCounts._fields_])
+        self.caps = caps
+        self.h = C.c_void_p()
+        check(self.L.gfpl_pgo_create(ctx.h, C.byref(self.caps), max_problems, C.byref(self.h)), "pgo_create")
+
+    def solve(self, problems, params: Optional[PoseGraphParams] = None, debug=None):
+        """Per problem a dict: result (PgoResult), T_kf [n_kf][4][4], x_kf [n_kf][6] (NaN rows: keyframes
+        the call did not move), pt, ls, pt_dirs / ls_dirs (per landmark, or None) and guards_ok (the
+        PGO_GUARD sentinels on either side of every device array are untouched).  The problems' own
+        arrays are not changed.  debug = i: also gfpl_pgo_debug_system of problem i (params.max_iters
+        must be 1), as the second element of a pair."""
+        import torch
+        prm = params if params is not None else PoseGraphParams.default()
+        n = len(problems)
+        dev = torch.device("cuda", self.ctx.device)
+        G, SENT = PGO_GUARD, -6.02214076e23
+        fulls, devs, structs = [], [], (PgoProblemStruct * max(n, 1))()
+        for i, p in enumerate(problems):
+            src = dict(p.a, x_kf=np.full((p.n_kf, 6), np.nan))
+            full, d = {}, {}
+            for k in PoseGraphProblem.DEVICE:
+                if src[k] is None:
+                    d[k] = None
+                    continue
+                h = np.concatenate([np.full(G, SENT), src[k].reshape(-1), np.full(G, SENT)])
+                full[k] = torch.from_numpy(h).to(dev)
+                d[k] = full[k][G:G + src[k].size]
+            fulls.append(full)
+            devs.append(d)
+            structs[i] = p.struct(d)
+        out = (PgoResult * max(n, 1))()
+        torch.cuda.synchronize()
+        check(self.L.gfpl_pgo_solve(self.h, structs, n, C.byref(prm), out), "pgo_solve")
+        res = []
+        for i, p in enumerate(problems):
+            host = {k: t.cpu().numpy() for k, t in fulls[i].items()}
+            ok = all((h[:G] == SENT).all() and (h[-G:] == SENT).all() for h in host.values())
+            get = lambda k, w: host[k][G:-G].reshape(-1, w).copy()
+            r = dict(result=PgoResult.from_buffer_copy(out[i]), T_kf=get("T_kf", 16).reshape(-1, 4, 4), x_kf=get("x_kf", 6),
+                     pt=get("pt", 3), ls=get("ls", 6), guards_ok=bool(ok))
+            for k in ("pt", "ls"):
+                if p.a[k + "_dir"] is None:
+                    r[k + "_dirs"] = None
+                else:
+                    rows, off = get(k + "_dir", 3), p.a[k + "_dir_off"]
+                    r[k + "_dirs"] = [rows[off[j]:off[j + 1]] for j in range(len(off) - 1)]
+            res.append(r)
+        if debug is None:
+            return res
+        rc, c = problems[debug].check(prm)
+        check(rc, "pgo_check")
+        sysd = dict(b=np.zeros(6 * c.n_free), diag=np.zeros((c.n_free, 6, 6)), env=np.zeros((c.env_blocks, 6, 6)),
+                    env_first=np.zeros(c.n_free, np.int32), vert=np.zeros((c.n_vert, 4), np.int32),
+                    edge=np.zeros((c.n_edge, 4), np.int32), Z=np.zeros((c.n_edge, 4, 4)), X0=np.zeros((c.n_vert, 4, 4)))
+        chi2 = C.c_double(0.0)
+        check(self.L.gfpl_pgo_debug_system(self.h, debug, C.byref(chi2), *[_ptr(sysd[k]) if sysd[k].size else None for k in (
+            "b", "diag", "env", "env_first", "vert", "edge", "Z", "X0")]), "pgo_debug_system")
+        sysd["chi2"] = np.float64(chi2.value)
+        # the dense lower triangle of the free system from the envelope rows
+        nf = c.n_free
+        H = np.zeros((6 * nf, 6 * nf))
+        o = 0
+        for r_ in range(nf):
+            f = int(sysd["env_first"][r_])
+            for cc in range(f, r_):
+                H[6 * r_:6 * r_ + 6, 6 * cc:6 * cc + 6] = sysd["env"][o + cc - f]
+            H[6 * r_:6 * r_ + 6, 6 * r_:6 * r_ + 6] = sysd["diag"][r_]
+            o += r_ - f + 1
+        sysd["H"] = H
+        return res, sysd
+
+    def ms(self):
+        """gfpl_pgo_debug_ms: device milliseconds (k_pgo, k_pgo_correct) of the last solve."""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        check(self.L.gfpl_pgo_debug_ms(self.h, C.byref(a), C.byref(b)), "pgo_debug_ms")
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            check(self.L.gfpl_pgo_destroy(self.h), "pgo_destroy")
             self.h = None
 
     def __del__(self):

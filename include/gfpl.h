@@ -974,6 +974,103 @@ int  gfpl_lba_solve(gfpl_lba* lba, const gfpl_lba_problem* problems, int n, cons
 int  gfpl_lba_debug_system(gfpl_lba* lba, int i, int iteration, double* U, double* g, double* V_pt, double* V_ls,
                            double* W_pt, double* W_ls, double* err);
 
+/* ------------------------------------------- loop-closure pose graph ----- */
+/* MapHandler::loopClosureOptimizationCovGraphG2O / EssGraphG2O (src/mapHandler.cpp:4187-4419,
+ * :3950-4184) for n problems in one call: the pose graph over the keyframes, its
+ * Levenberg-Marquardt solve (k_pgo, one workgroup per problem) and the rigid correction of every
+ * keyframe pose and every landmark that hangs on it (k_pgo_correct).  The graph (vertices, flags,
+ * edge order), the measurements, the start poses and the map correction are the reference's.  The
+ * objective and the iteration are pinned by DESIGN.md §4j (ledger PG1-PG8), not by g2o, which the
+ * reference tree does not contain.  Not here: loopClosureFuseLandmarks, per-edge information
+ * matrices (the reference passes identity), globalBundleAdjustment.                             */
+#define GFPL_PGO_COV 0          /* loopClosureOptimizationCovGraphG2O */
+#define GFPL_PGO_ESS 1          /* loopClosureOptimizationEssGraphG2O */
+typedef struct gfpl_pgo gfpl_pgo;
+/* Config::minLMEssGraph, minLMCovGraph (100, 30: src/config.cpp:50-51), the variant, and the
+ * iteration: optimize(100), setUserLambdaInit(1e-10), at most max_rejects damped retries of a step */
+typedef struct gfpl_pgo_graph_params {
+    int32_t min_lm_ess_graph, min_lm_cov_graph, variant, max_iters, max_rejects, pad;
+    double  lambda_init;
+} gfpl_pgo_graph_params;
+void gfpl_default_pgo_params(gfpl_pgo_graph_params* prm);   /* 100, 30, COV, 100, 10, 1e-10 */
+/* What a problem takes: keyframes, loop entries, vertices, free vertices, edges, 6 x 6 blocks of the
+ * envelope (row r of the free system is stored from its first column f(r) to r), and the landmarks
+ * of the point / line ownership lists that are not freed.  As caps of gfpl_pgo_create only n_kf,
+ * n_lc, n_edge, env_blocks, n_pt and n_ls are read (n_vert, n_free <= n_kf).                    */
+typedef struct gfpl_pgo_counts { int32_t n_kf, n_lc, n_vert, n_free, n_edge, env_blocks, n_pt, n_ls; } gfpl_pgo_counts;
+/* One problem.  The doubles of the map are DEVICE arrays, in and out; the index arrays, the loop
+ * list and lc_pose are HOST arrays (the caller's graph bookkeeping; checked before any device work
+ * and uploaded).  A landmark belongs to one keyframe: *_kf_idx[*_kf_start[i] .. *_kf_start[i + 1])
+ * are map_points_kf_idx[i] / map_lines_kf_idx[i]; an entry < 0, or one whose *_freed byte is set, is a
+ * freed landmark (map_points[.] == NULL) and is skipped.  *_dir: every landmark's dir_list rows in
+ * one array, landmark j's at rows [*_dir_off[j], *_dir_off[j + 1]); NULL (both) when the caller
+ * does not keep them on the device.  med_obs_dir is not provided (ledger LM6).                  */
+typedef struct gfpl_pgo_problem {
+    int32_t        n_kf, n_lc;      /* map_keyframes.size(), lc_idx_list.size()                    */
+    int32_t        n_pt, n_ls;      /* rows of pt / ls (the landmark ids of the lists are < these) */
+    const uint8_t* alive;           /* HOST [n_kf]: map_keyframes[i] != NULL                       */
+    const int32_t* full_graph;      /* HOST [n_kf][n_kf]                                           */
+    const int32_t* lc;              /* HOST [n_lc][3]: kf_prev, kf_curr, flag                      */
+    const double*  lc_pose;         /* HOST [n_lc][6]: lc_pose_list                                */
+    double*        T_kf;            /* [n_kf][16] in / out: T_kf_w                                 */
+    double*        x_kf;            /* [n_kf][6]  out: x_kf_w of every keyframe the call moved     */
+    double*        pt;              /* [n_pt][3]  in / out: point3D (may be NULL when n_pt = 0)    */
+    double*        ls;              /* [n_ls][6]  in / out: line3D                                 */
+    double*        pt_dir;          /* [.][3]     in / out, or NULL                                */
+    double*        ls_dir;          /* [.][3]     in / out, or NULL                                */
+    const int32_t* pt_kf_start;     /* HOST [n_kf + 1], or NULL when n_pt = 0                      */
+    const int32_t* pt_kf_idx;       /* HOST [pt_kf_start[n_kf]]                                    */
+    const int32_t* ls_kf_start;     /* HOST [n_kf + 1], or NULL when n_ls = 0                      */
+    const int32_t* ls_kf_idx;       /* HOST [ls_kf_start[n_kf]]                                    */
+    const int32_t* pt_dir_off;      /* HOST [n_pt + 1], read when pt_dir is given                  */
+    const int32_t* ls_dir_off;      /* HOST [n_ls + 1], read when ls_dir is given                  */
+    const uint8_t* pt_freed;        /* HOST [n_pt] or NULL                                         */
+    const uint8_t* ls_freed;        /* HOST [n_ls] or NULL                                         */
+} gfpl_pgo_problem;
+#define GFPL_PGO_STOP_ITERS  0  /* max_iters iterations ran                                        */
+#define GFPL_PGO_STOP_STEP   1  /* |delta|_inf <= 64 DBL_EPSILON: the step is not applied          */
+#define GFPL_PGO_STOP_DCHI2  2  /* an accepted step lowered chi2 by <= 64 DBL_EPSILON chi2         */
+#define GFPL_PGO_STOP_REJECT 3  /* max_rejects trials of one iteration were rejected               */
+#define GFPL_PGO_STOP_NOFREE 4  /* no free vertex: nothing to solve (iters = 0)                    */
+#define GFPL_PGO_SINGULAR    1  /* status: a pivot that was not positive and finite (a rejected trial) */
+typedef struct gfpl_pgo_result {
+    int32_t iters, stop, status, rejects;   /* rejects: rejected trials over the whole solve       */
+    int32_t n_vert, n_free, n_edge, kf_curr;
+    double  lambda, chi2_0, chi2;
+} gfpl_pgo_result;
+/* Host only, no device.  Builds the graph and returns its counts (may be NULL).  GFPL_E_INVALID: a
+ * NULL pointer, n_kf < 1, an empty loop list, a loop entry outside [0, n_kf) or with kf_prev >=
+ * kf_curr, a dead keyframe named by a loop entry, keyframe 0 dead in COV, a negative threshold, a
+ * variant other than COV / ESS, an ownership list that does not ascend from 0, names a landmark
+ * >= n_pt / n_ls or names one twice, dir offsets that do not ascend from 0.                     */
+int  gfpl_pgo_check(const gfpl_pgo_problem* p, const gfpl_pgo_graph_params* prm, gfpl_pgo_counts* counts);
+/* Host only: the device workspace one problem of these counts takes and the kernel's dynamic LDS. */
+int  gfpl_pgo_workspace(const gfpl_pgo_counts* n, int64_t* hbm_bytes, int32_t* lds_bytes);
+/* caps: the largest counts of one problem; room for max_problems of them.  The context cannot be
+ * destroyed while the object lives.                                                             */
+int  gfpl_pgo_create(gfpl_ctx* ctx, const gfpl_pgo_counts* caps, int max_problems, gfpl_pgo** out);
+int  gfpl_pgo_destroy(gfpl_pgo* pgo);
+/* problems, results: HOST arrays of n.  Every problem is checked (gfpl_pgo_check) before any device
+ * work; GFPL_E_CAPACITY when n or a count exceeds what the object was created for; a refused call
+ * changes nothing and leaves the object usable.  Synchronises once.  GFPL_E_HIP from a copy, launch
+ * or synchronisation leaves the map's contents unknown: solve and the debug calls return
+ * GFPL_E_STATE from then on and the object can only be destroyed.                               */
+int  gfpl_pgo_solve(gfpl_pgo* pgo, const gfpl_pgo_problem* problems, int n, const gfpl_pgo_graph_params* prm,
+                    gfpl_pgo_result* results);
+/* Test hook: problem i of the last gfpl_pgo_solve, which must have run with max_iters = 1 so that
+ * the system it leaves is iteration 0's (GFPL_E_STATE otherwise, or when that solve had fewer
+ * problems).  HOST outputs, any may be NULL: chi2 and b [6 n_free], diag [n_free][6][6], env
+ * [env_blocks][6][6] (the undamped envelope rows; row r's last block is the zeroed place of its
+ * diagonal block), env_first [n_free], vert [n_vert][4] (keyframe, flags: bit 0 fixed, 1 is_lc_j,
+ * 2 is_lc_i, lc_id or -1, free index or -1), edge [n_edge][4] (vertex i, vertex j, loop entry or
+ * -1, 0), Z [n_edge][16], X0 [n_vert][16] (the start poses).  With no free vertex nothing of the
+ * system but chi2 is written.                                                                   */
+int  gfpl_pgo_debug_system(gfpl_pgo* pgo, int i, double* chi2, double* b, double* diag, double* env,
+                           int32_t* env_first, int32_t* vert, int32_t* edge, double* Z, double* X0);
+/* Instrumentation (tools/bench_pgo.py): device milliseconds of k_pgo and of k_pgo_correct in the
+ * last solve; GFPL_E_STATE when there is none.                                                  */
+int  gfpl_pgo_debug_ms(gfpl_pgo* pgo, float* ms_solve, float* ms_correct);
+
 /* ----------------------------------------------------- state transfer ----- */
 /* Copy one sequence's frame state device -> host (synchronises).            */
 int  gfpl_read_frame(gfpl_seqbatch* sb, int which, int seq, gfpl_frame_host* out);
