@@ -161,6 +161,45 @@ struct LbaArgs {
 };
 hipError_t launch_lba(const LbaArgs& a, int n, hipStream_t s);
 
+// levMarquardtOptimizationGBA (k_gba.hip): one problem over many workgroups; all pointers device.
+// The index arrays are GbaIdx's uploaded copies of the planner's lists, m the workspace (GbaMem).
+// THE RULES THAT DIFFER FROM THE LBA live in GbaRules, read by the kernels at the four places they
+// bind (ledger GB3, GB5, GB7, GB9); gfpl_gba_solve passes GBA_RULES_REFERENCE.
+struct GbaRules {
+    int divisor_zero;         // the iterations divide err by Npt_obs + Nls_obs = 0 (else by Npt + Nls, the LBA's)
+    int line_th_homog;        // the iterations' line terms keep homogTh (else 1e-7, the LBA's)
+    int prepass_transposed;   // the pre-pass writes a line's coupling block under the diagonal transposed
+    int any_sign_pivot;       // a finite non-zero pivot of S of either sign is accepted (else positive only, BA13)
+};
+constexpr GbaRules GBA_RULES_REFERENCE{1, 1, 1, 1};
+struct GbaProb {
+    gfpl_gba_counts n;
+    const double* x_kf;
+    double* T_kf;
+    const double* T_fix;
+    double *pt, *ls;
+    const double *pt_obs, *pt_sigma, *ls_obs, *ls_sigma;
+    double* x_out;
+    const int32_t *lm_start, *obs_lm, *obs_kf, *obs_pair, *pair_start, *pair_kf, *kf_start, *kf_obs, *blk_start, *terms;
+    GbaPtrs m;
+};
+struct GbaArgs {
+    DevCam cam;                   // fx, fy, cx, cy are read
+    double homog_th;
+    gfpl_lba_params prm;
+    GbaRules rules;
+    GbaProb pr;
+    gfpl_lba_result* out;         // the problem's record
+};
+// how the wide phases are cut into workgroups; no result depends on it (tests/test_gba_gpu.py)
+struct GbaGrid {
+    int block = GBA_BLOCK;        // threads per workgroup of the per-observation / per-landmark phases: 64 .. 256
+    int ldlt_kfs = GBA_LDLT_KFS;  // block rows per workgroup of k_gba_ldlt: 1 .. GBA_MAX_LDLT_ROWS
+};
+// every launch of one problem's solve, all iterations, in stream order; nothing is synchronised
+hipError_t enqueue_gba(const GbaArgs& a, const GbaGrid& grid, hipStream_t s);
+int gba_max_lds_bytes(int n_kf);
+
 // the landmark descriptor store (k_lm.hip); all pointers device.  The store's arrays are LmStoreMem's,
 // work / ops LmWorkMem's.
 struct LmStoreDev {

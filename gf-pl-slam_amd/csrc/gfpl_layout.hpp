@@ -419,4 +419,89 @@ struct PgoLds {
     GFPL_HD explicit PgoLds(unsigned char* smem) : c(smem) {}
 };
 
+// ---- global bundle adjustment (k_gba.hip, gfpl_gba.cpp, gfpl_gba_plan.cpp): one problem spread over
+// the device.  Landmarks and observations are numbered as in the LBA (points first).  A coupling
+// block W (and Y = V^-1 W) exists once per PAIR (landmark, distinct local keyframe that observes
+// it), pairs ordered by landmark and then by keyframe: point pairs first at 18 doubles each, line
+// pairs after them at 36.  S is the dense reduced pose system, row-major 6 n_kf square in HBM; its
+// lower triangle becomes L in place outside the 6 x 6 diagonal blocks, whose L is kept transposed above
+// the diagonal (the block under it stays what every workgroup of its column's launch reads); the pivots go to D.
+constexpr int GBA_BLOCK = 256;     // threads of the wide phases, terms per pass of the ordered sums, rows per pass of the substitutions
+constexpr int GBA_ROW = LBA_ROW;   // an observation row is the LBA's
+constexpr int GBA_LDLT_KFS = 6;    // block rows of the panel one workgroup of k_gba_ldlt factorises (below its copy of the diagonal block)
+constexpr int GBA_MAX_KFS = 256;   // = GFPL_GBA_MAX_KFS (gfpl_gba.cpp asserts it)
+constexpr int GBA_MAX_LDLT_ROWS = 24;   // the test override of GBA_LDLT_KFS: 36 (1 + rows) threads stay within 1024
+// slots of the loop state (GbaPtrs::sd, ::si)
+enum { GBA_SD_LAMBDA = 0, GBA_SD_ERR, GBA_SD_ERRPREV, GBA_SD_ERRSUM, GBA_SD_N2, GBA_SD_N2POSE };
+enum { GBA_SI_ITERS = 0, GBA_SI_STOP, GBA_SI_STATUS, GBA_SI_HMAX, GBA_SI_DONE, GBA_SI_DONE_NEXT, GBA_SI_SING, GBA_SI_UPDATE_IT,
+       GBA_SI_LAST_IT, GBA_SI_LDLT_BAD0, GBA_SI_LDLT_BAD1 };
+// the planner's index arrays of one problem, laid out alike in the pinned staging and on the device
+struct GbaIdx {
+    Carver c;
+    int nkf, nlm, nobs, npairs, nterms;
+    int32_t* lm_start = c.take<int32_t>((size_t)nlm + 1);      // first observation of each landmark
+    int32_t* obs_lm = c.take<int32_t>((size_t)nobs);
+    int32_t* obs_kf = c.take<int32_t>((size_t)nobs);           // slot: >= 0 local, < 0 fixed
+    int32_t* obs_pair = c.take<int32_t>((size_t)nobs);         // the observation's pair, -1 for a fixed pose
+    int32_t* pair_start = c.take<int32_t>((size_t)nlm + 1);    // pairs of each landmark
+    int32_t* pair_kf = c.take<int32_t>((size_t)npairs);        // ascending within a landmark
+    int32_t* kf_start = c.take<int32_t>((size_t)nkf + 1);      // observations of each local keyframe, list order
+    int32_t* kf_obs = c.take<int32_t>((size_t)nobs);
+    int32_t* blk_start = c.take<int32_t>((size_t)nkf * (nkf + 1) / 2 + 1);   // terms of lower block (a, b): index a (a + 1) / 2 + b
+    int32_t* terms = c.take<int32_t>((size_t)nterms * 3);      // landmark (ascending within a block), pair of a, pair of b
+    size_t bytes = (c.off + 255) & ~(size_t)255;
+    GbaIdx(char* base, int nkf, int nlm, int nobs, int npairs, int nterms)
+        : c{0, base}, nkf(nkf), nlm(nlm), nobs(nobs), npairs(npairs), nterms(nterms) {}
+};
+struct GbaPtrs {
+    double *X, *DX;               // [6 n_kf + 3 n_pt + 6 n_ls]
+    double* rows;                 // [n_obs][GBA_ROW]
+    double* Tinv;                 // [n_kf][16] inverse poses of X, once per iteration
+    double *U, *gk;               // [n_kf][36], [n_kf][6]
+    double *V, *Vi;               // [9 n_pt + 36 n_ls]: undamped blocks; LDL^T of the damped ones (L under, pivots on the diagonal)
+    double *glm, *z;              // [3 n_pt + 6 n_ls]
+    double *W, *Y;                // [18 n_pt_pairs + 36 n_ls_pairs]
+    double *q, *dmax;             // [n_lm] squared step, largest |diagonal| of each landmark
+    double *S, *D, *gr;           // [6 n_kf][6 n_kf], [6 n_kf], [6 n_kf]: g_r, then the pose step
+    double* sd;                   // [8]  GBA_SD_*
+    int32_t* si;                  // [16] GBA_SI_*
+};
+struct GbaMem {
+    Carver c;
+    int nkf, npt, nls, nobs, npp, nlp;
+    size_t N = 6 * (size_t)nkf + 3 * (size_t)npt + 6 * (size_t)nls;
+    size_t nv = 9 * (size_t)npt + 36 * (size_t)nls, ng = 3 * (size_t)npt + 6 * (size_t)nls;
+    size_t nw = 18 * (size_t)npp + 36 * (size_t)nlp, n6 = 6 * (size_t)nkf;
+    GbaPtrs p{c.take<double>(N), c.take<double>(N), c.take<double>((size_t)nobs * GBA_ROW), c.take<double>((size_t)nkf * 16),
+              c.take<double>((size_t)nkf * 36), c.take<double>(n6),
+              c.take<double>(nv), c.take<double>(nv), c.take<double>(ng), c.take<double>(ng),
+              c.take<double>(nw), c.take<double>(nw), c.take<double>((size_t)npt + nls), c.take<double>((size_t)npt + nls),
+              c.take<double>(n6 * n6), c.take<double>(n6), c.take<double>(n6),
+              c.take<double>(8), c.take<int32_t>(16)};
+    size_t bytes = (c.off + 255) & ~(size_t)255;
+    GbaMem(char* base, int nkf, int npt, int nls, int nobs, int npp, int nlp)
+        : c{0, base}, nkf(nkf), npt(npt), nls(nls), nobs(nobs), npp(npp), nlp(nlp) {}
+};
+// ---- k_gba_ldlt: the partial sums of the diagonal block's and the panel's entries, then the factor
+// of the diagonal block and its pivots; rows: 6 + 6 * (block rows per workgroup)
+struct GbaLdltLds {
+    LdsCarver c;
+    int rows;
+    double* part = c.take<double>(rows * 6);
+    double* Ld = c.take<double>(36);
+    double* Dd = c.take<double>(6);
+    int* flag = c.take<int>(2);
+    int bytes = c.off;
+    GFPL_HD GbaLdltLds(unsigned char* smem, int rows) : c(smem), rows(rows) {}
+};
+// ---- k_gba_subst: the right-hand side / solution of the reduced system
+struct GbaSubstLds {
+    LdsCarver c;
+    int n6;
+    double* y = c.take<double>(n6);
+    int bytes = c.off;
+    GFPL_HD GbaSubstLds(unsigned char* smem, int n6) : c(smem), n6(n6) {}
+};
+static_assert(8 * 6 * GBA_MAX_KFS <= 64 * 1024, "GbaSubstLds at GBA_MAX_KFS fits the default dynamic LDS");
+
 }  // namespace gfpl

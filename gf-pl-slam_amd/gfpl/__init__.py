@@ -330,6 +330,44 @@ def lbaWorkspace(n_kf, n_fix, n_pt, n_ls, n_pt_obs, n_ls_obs):
     return rc, hbm.value, lds.value
 
 
+GBA_MAX_KFS = 256   # GFPL_GBA_MAX_KFS
+GBA_STOP_ITERS, GBA_STOP_DERR, GBA_STOP_ERR, GBA_STOP_STEP = 0, 1, 2, 3
+GBA_SINGULAR, GBA_HMAX_RANGE, GBA_INDEFINITE = 1, 2, 4
+
+
+class GbaCounts(C.Structure):
+    """gfpl_gba_counts: a problem's counts, its (landmark, keyframe) pairs and the terms of S."""
+    _fields_ = [("n", LbaCounts), ("n_pt_pairs", C.c_int32), ("n_ls_pairs", C.c_int32), ("n_terms", C.c_int32),
+                ("pad", C.c_int32)]
+
+    @classmethod
+    def of(cls, n_kf, n_fix, n_pt, n_ls, n_pt_obs, n_ls_obs, n_pt_pairs, n_ls_pairs, n_terms) -> "GbaCounts":
+        return cls(LbaCounts(n_kf, n_fix, n_pt, n_ls, n_pt_obs, n_ls_obs), n_pt_pairs, n_ls_pairs, n_terms, 0)
+
+    def flat(self):
+        return [getattr(self.n, f) for f, _ in LbaCounts._fields_] + [self.n_pt_pairs, self.n_ls_pairs, self.n_terms]
+
+
+GbaParams = LbaParams   # gfpl_gba_params: the GBA reads lambdaLbaLM, lambdaLbaK, maxItersLba too
+GbaResult = LbaResult   # gfpl_gba_result; status bits GBA_SINGULAR / GBA_HMAX_RANGE / GBA_INDEFINITE
+
+
+def gbaCheck(problem: LbaProblem):
+    """gfpl_gba_check on an LbaProblem (host only): (return code, GbaCounts the problem takes)."""
+    cnt = GbaCounts()
+    rc = hiplib().gfpl_gba_check(C.byref(problem.struct()), C.byref(cnt))
+    return rc, cnt
+
+
+def gbaWorkspace(counts):
+    """gfpl_gba_workspace: (return code, hbm_bytes, lds_bytes) for one problem of these counts (a
+    GbaCounts, or the nine numbers of GbaCounts.of)."""
+    cnt = counts if isinstance(counts, GbaCounts) else GbaCounts.of(*[int(v) for v in counts])
+    hbm, lds = C.c_int64(0), C.c_int32(0)
+    rc = hiplib().gfpl_gba_workspace(C.byref(cnt), C.byref(hbm), C.byref(lds))
+    return rc, hbm.value, lds.value
+
+
 # DBoW2::WeightingType and the keyframe database's modes (include/gfpl.h)
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3
 BOW_L1_NORM = 0
@@ -634,6 +672,13 @@ def hiplib() -> C.CDLL:
             "gfpl_lmstore_gather": ([P, P, C.c_int, P, P], C.c_int),
             "gfpl_lmstore_read": ([P, C.c_int, P, P, P, P], C.c_int),
             "gfpl_lmstore_debug_ms": ([P, P], C.c_int),
+            "gfpl_default_gba_params": ([P], None),
+            "gfpl_gba_check": ([P, P], C.c_int),
+            "gfpl_gba_workspace": ([P, P, P], C.c_int),
+            "gfpl_gba_create": ([P, P, C.c_int, C.POINTER(P)], C.c_int),
+            "gfpl_gba_destroy": ([P], C.c_int),
+            "gfpl_gba_solve": ([P, P, C.c_int, P, P], C.c_int),
+            "gfpl_gba_debug_system": ([P, C.c_int, C.c_int, P, P, P, P, P, P, P, P], C.c_int),
             "gfpl_default_pgo_params": ([P], None),
             "gfpl_pgo_check": ([P, P, P], C.c_int),
             "gfpl_pgo_workspace": ([P, P, P], C.c_int),
@@ -1189,6 +1234,37 @@ class Context:
         prm.max_iters = iteration + 1
         return self._lba_run([problem], prm, debug=(0, iteration))[1]
 
+    def _gba_run(self, problems, prm, debug=None):
+        counts = []
+        for p in problems:   # the host rules first: nothing is allocated for a refused problem
+            rc, c = gbaCheck(p)
+            if rc != 0:
+                raise GfplError(rc, "gba_check")
+            counts.append(c.flat())
+        caps = [max(col) for col in zip(*counts)] if counts else [1, 0, 0, 0, 0, 0, 0, 0, 0]
+        solver = GbaSolver(self, caps, max(len(problems), 1))
+        try:
+            return solver.solve(problems, prm, debug)
+        finally:
+            solver.close()
+
+    def globalBundleAdjustment(self, problems, params: Optional[LbaParams] = None):
+        """MapHandler::globalBundleAdjustment's solver (levMarquardtOptimizationGBA, src/mapHandler.cpp:
+        1950-2544) for one LbaProblem or a list of them: the local keyframes are every alive keyframe but
+        keyframe 0, which is a fixed pose.  Per problem the dict of Context.localBundleAdjustment.  The
+        problems' own arrays are not changed."""
+        single = isinstance(problems, LbaProblem)
+        res = self._gba_run([problems] if single else list(problems), params if params is not None else LbaParams.default())
+        return res[0] if single else res
+
+    def gbaDebugSystem(self, problem: LbaProblem, iteration: int, params: Optional[LbaParams] = None):
+        """Test hook (gfpl_gba_debug_system): the undamped system of `iteration` (0: the pre-pass) from a
+        solve of iteration + 1 iterations: U, g, V_pt, V_ls, err, and the coupling blocks under the
+        diagonal per (landmark, keyframe) pair: W_pt [point pairs][3][6], W_ls [line pairs][6][6], pairs."""
+        prm = LbaParams.default() if params is None else LbaParams.from_buffer_copy(params)
+        prm.max_iters = iteration + 1
+        return self._gba_run([problem], prm, debug=(0, iteration))[1]
+
     def _pgo_run(self, problems, prm, debug=None):
         counts = []
         for p in problems:   # the host rules first: nothing is allocated for a refused problem
@@ -1262,6 +1338,65 @@ class Event:
     def close(self):
         if getattr(self, "h", None):
             self.L.gfpl_event_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GbaSolver:
+    """gfpl_gba: the device workspace of up to max_problems global bundle adjustments whose counts
+    (GbaCounts, or the nine numbers of GbaCounts.of) stay within caps; solve() may be called any number
+    of times.  The context cannot be closed while the solver is open."""
+
+    def __init__(self, ctx: "Context", caps, max_problems: int):
+        self.ctx, self.L = ctx, ctx.L
+        self.caps = caps if isinstance(caps, GbaCounts) else GbaCounts.of(*[int(v) for v in caps])
+        self.h = C.c_void_p()
+        check(self.L.gfpl_gba_create(ctx.h, C.byref(self.caps), max_problems, C.byref(self.h)), "gba_create")
+
+    def solve(self, problems, params: Optional[LbaParams] = None, debug=None):
+        """Per problem a dict (see Context.globalBundleAdjustment).  debug = (i, iteration): also the
+        system of gfpl_gba_debug_system for problem i, as the second element of a pair."""
+        import torch
+        prm = params if params is not None else LbaParams.default()
+        n = len(problems)
+        dev = torch.device("cuda", self.ctx.device)
+        devs, structs = [], (LbaProblemStruct * max(n, 1))()
+        for i, p in enumerate(problems):
+            d = {k: torch.from_numpy(p.a[k].copy()).to(dev) for k, _ in LBA_DOUBLES}
+            d["x_out"] = d["x_kf"].clone()   # (a problem whose Hmax leaves the int range writes nothing)
+            devs.append(d)
+            structs[i] = p.struct(d)
+        out = (LbaResult * max(n, 1))()
+        torch.cuda.synchronize()
+        check(self.L.gfpl_gba_solve(self.h, structs, n, C.byref(prm), out), "gba_solve")
+        res = []
+        for i, d in enumerate(devs):
+            res.append(dict(result=LbaResult.from_buffer_copy(out[i]), T_kf=d["T_kf"].cpu().numpy().reshape(-1, 4, 4),
+                            pt=d["pt"].cpu().numpy(), ls=d["ls"].cpu().numpy(), x_kf=d["x_out"].cpu().numpy()))
+        if debug is None:
+            return res
+        i, it = debug
+        rc, g = gbaCheck(problems[i])
+        check(rc, "gba_check")
+        c = g.n
+        sysd = dict(U=np.zeros((c.n_kf, 6, 6)), g=np.zeros(6 * c.n_kf + 3 * c.n_pt + 6 * c.n_ls),
+                    V_pt=np.zeros((c.n_pt, 3, 3)), V_ls=np.zeros((c.n_ls, 6, 6)),
+                    W_pt=np.zeros((g.n_pt_pairs, 3, 6)), W_ls=np.zeros((g.n_ls_pairs, 6, 6)),
+                    pairs=np.zeros((g.n_pt_pairs + g.n_ls_pairs, 2), np.int32))
+        err = C.c_double(0.0)
+        check(self.L.gfpl_gba_debug_system(self.h, i, it, *[_ptr(sysd[k]) for k in ("U", "g", "V_pt", "V_ls", "W_pt", "W_ls", "pairs")],
+                                           C.byref(err)), "gba_debug_system")
+        sysd["err"] = np.float64(err.value)
+        return res, sysd
+
+    def close(self):
+        if getattr(self, "h", None):
+            check(self.L.gfpl_gba_destroy(self.h), "gba_destroy")
             self.h = None
 
     def __del__(self):

@@ -974,6 +974,62 @@ int  gfpl_lba_solve(gfpl_lba* lba, const gfpl_lba_problem* problems, int n, cons
 int  gfpl_lba_debug_system(gfpl_lba* lba, int i, int iteration, double* U, double* g, double* V_pt, double* V_ls,
                            double* W_pt, double* W_ls, double* err);
 
+/* ------------------------------------------ global bundle adjustment ----- */
+/* MapHandler::globalBundleAdjustment's solver levMarquardtOptimizationGBA (src/mapHandler.cpp:
+ * 1950-2544) over a whole map: one problem spreads over the device, phase by phase, as separate
+ * launches in stream order (k_gba.hip).  A problem is a gfpl_lba_problem: the local
+ * keyframes are every alive keyframe but keyframe 0 (:1851-1863), keyframe 0 is a fixed pose, and
+ * an observation whose keyframe is dead is left out by the caller (:1981).  H, g and err of every
+ * iteration have the reference's bits, its quirks included (ledger GB1-GB12): err is divided by
+ * counters that stay 0, so it is +inf or NaN, no error stop fires and every step is applied; the
+ * pre-pass writes a line's coupling block transposed, so its system can be indefinite.  The solve
+ * is the project's own elimination (landmark blocks first, each through its own LDL^T, then a dense
+ * LDL^T of the reduced pose system without pivoting), reading the lower triangle of H as
+ * SimplicialLDLT does.                                                                          */
+#define GFPL_GBA_MAX_KFS 256  /* local keyframes per problem.  Bounded by the dense reduced system S in
+                                 HBM ((6 n_kf)^2 doubles: 18.9 MB at 256, four times that at 512) and by
+                                 the time of its factorisation (n_kf launches of O(n_kf^2) work each per
+                                 iteration: cubic in n_kf, about 20 iterations per solve)          */
+typedef struct gfpl_gba gfpl_gba;
+typedef gfpl_lba_params gfpl_gba_params;    /* the GBA reads lambdaLbaLM, lambdaLbaK, maxItersLba (:1965-1966) */
+typedef gfpl_lba_result gfpl_gba_result;
+void gfpl_default_gba_params(gfpl_gba_params* prm);
+/* n: a problem's counts; n_pt_pairs / n_ls_pairs: (landmark, distinct local keyframe) pairs of the
+ * points / lines, one W and one Y block each; n_terms: contributing terms of S, one per landmark
+ * and lower block (a >= b) whose two keyframes both observe it.                                 */
+typedef struct gfpl_gba_counts { gfpl_lba_counts n; int32_t n_pt_pairs, n_ls_pairs, n_terms, pad; } gfpl_gba_counts;
+#define GFPL_GBA_STOP_ITERS 0
+#define GFPL_GBA_STOP_DERR  1   /* cannot fire: err is +inf or NaN (ledger GB3)                 */
+#define GFPL_GBA_STOP_ERR   2   /* cannot fire                                                  */
+#define GFPL_GBA_STOP_STEP  3   /* |DX| < DBL_EPSILON                                           */
+#define GFPL_GBA_SINGULAR   1   /* status: a zero or non-finite pivot of S, or a damped landmark diagonal or a
+                                   pivot of a landmark block that is not positive and finite; that step is dropped */
+#define GFPL_GBA_HMAX_RANGE 2   /* status: as GFPL_LBA_HMAX_RANGE                               */
+#define GFPL_GBA_INDEFINITE 4   /* status, informational: a negative pivot of S was accepted    */
+/* Host only, no device: everything gfpl_lba_check refuses, with GFPL_E_CAPACITY for n_kf >
+ * GFPL_GBA_MAX_KFS or a pair / term count beyond 32 bits; counts (may be NULL) is what the problem
+ * takes of a gfpl_gba object.                                                                   */
+int  gfpl_gba_check(const gfpl_lba_problem* p, gfpl_gba_counts* counts);
+/* Host only: the device workspace one problem of these counts takes and the largest dynamic LDS of
+ * any kernel.                                                                                   */
+int  gfpl_gba_workspace(const gfpl_gba_counts* n, int64_t* hbm_bytes, int32_t* lds_bytes);
+/* caps: the largest counts of one problem; room for max_problems of them.  The context needs a
+ * camera (GFPL_E_STATE) and cannot be destroyed while the object lives.                        */
+int  gfpl_gba_create(gfpl_ctx* ctx, const gfpl_gba_counts* caps, int max_problems, gfpl_gba** out);
+int  gfpl_gba_destroy(gfpl_gba* gba);
+/* problems, results: HOST arrays of n.  Every problem is checked and planned before any device
+ * work; GFPL_E_CAPACITY when n or a count exceeds the caps; a refused call changes nothing.  The
+ * problems run one after another in stream order; the call synchronises once.  After GFPL_E_HIP the
+ * map's contents are unknown and the object returns GFPL_E_STATE until it is destroyed.         */
+int  gfpl_gba_solve(gfpl_gba* gba, const gfpl_lba_problem* problems, int n, const gfpl_gba_params* prm,
+                    gfpl_gba_result* results);
+/* Test hook, as gfpl_lba_debug_system, of the LAST iteration problem i evaluated.  W_pt [point
+ * pairs][3][6] and W_ls [line pairs][6][6] are the coupling blocks under the diagonal (landmark rows,
+ * pose columns), one per pair in the planner's order; pairs [n_pt_pairs + n_ls_pairs][2] = (landmark in the unified
+ * numbering, points first; local keyframe).  Iteration 0 shows the transposed line blocks.       */
+int  gfpl_gba_debug_system(gfpl_gba* gba, int i, int iteration, double* U, double* g, double* V_pt, double* V_ls,
+                           double* W_pt, double* W_ls, int32_t* pairs, double* err);
+
 /* ------------------------------------------- loop-closure pose graph ----- */
 /* MapHandler::loopClosureOptimizationCovGraphG2O / EssGraphG2O (src/mapHandler.cpp:4187-4419,
  * :3950-4184) for n problems in one call: the pose graph over the keyframes, its
