@@ -33,6 +33,12 @@ struct gfpl_ctx {
     // created and destroyed from different host threads
     std::atomic<int> n_detectors{0};
     std::mutex host_mu;   // the host-buffer matchers (gfpl_*_host): one call at a time per context
+    // gfpl_map_fuse_search's workspace (grown on demand) and the pinned words its counts arrive in
+    char* fuse_ws = nullptr;
+    size_t fuse_ws_bytes = 0;
+    int* fuse_host = nullptr;
+    hipEvent_t fuse_ev[2][4]{};   // per kind: before select, after it, after the knn-2, after the gate (gfpl_map_fuse_debug_ms)
+    bool fuse_timed[2] = {false, false};
 };
 
 struct gfpl_seqbatch {
@@ -341,6 +347,15 @@ int gfpl_destroy(gfpl_ctx* c) {
     if (c->n_detectors.load() != 0) return GFPL_E_STATE;   // so do its ORB / LBD / LSD objects
     for (int i = 0; i < GFPL_NEV; ++i)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
+    for (int k = 0; k < 2; ++k)
+        for (int i = 0; i < 4; ++i)
+            if (c->fuse_ev[k][i]) (void)hipEventDestroy(c->fuse_ev[k][i]);
+    if (c->fuse_ws || c->fuse_host) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        if (c->fuse_ws) (void)hipFree(c->fuse_ws);
+        if (c->fuse_host) (void)hipHostFree(c->fuse_host);
+    }
     if (c->own_stream) {
         (void)hipStreamSynchronize(c->stream);
         (void)hipStreamDestroy(c->stream);
@@ -1114,6 +1129,116 @@ int gfpl_kf_local_map_matches(gfpl_ctx* c, const gfpl_map_view* m, const gfpl_kf
     if (e != hipSuccess || ef != hipSuccess) return GFPL_E_HIP;
     *n_pt_pairs = counts[0];
     *n_ls_pairs = counts[1];
+    return GFPL_OK;
+}
+
+void gfpl_default_fuse_params(gfpl_fuse_params* p) {
+    if (!p) return;
+    p->max_point_point_error = 0.1;   // src/config.cpp:46-48
+    p->max_point_line_error = 0.1;
+    p->max_dir_line_error = 0.1;
+}
+
+// fuseLandmarksFromLocalMap's candidate search (src/mapHandler.cpp:859-1056): per kind one select
+// launch, one knn-2 launch of the selected rows against themselves with the count read on the
+// device, one gate launch (k_fuse.hip); the counts of both kinds arrive with one synchronisation.
+int gfpl_map_fuse_search(gfpl_ctx* c, const gfpl_fuse_map* m, const gfpl_fuse_params* prm, int32_t* pt_loc, int* n_pt_loc,
+                         int32_t* pt_pairs, int* n_pt_pairs, int32_t* ls_loc, int* n_ls_loc, int32_t* ls_pairs,
+                         int* n_ls_pairs) {
+    if (!c || !m || !prm || !n_pt_loc || !n_pt_pairs || !n_ls_loc || !n_ls_pairs || !c->has_cam) return GFPL_E_INVALID;
+    const int n[2] = {m->map.n_pt, m->map.n_ls};
+    if (n[0] < 0 || n[1] < 0 || m->n_kf < 0) return GFPL_E_INVALID;
+    *n_pt_loc = *n_pt_pairs = *n_ls_loc = *n_ls_pairs = 0;
+    const uint8_t* desc[2] = {m->map.pdesc, m->map.ldesc};
+    const double* X[2] = {m->map.P, m->map.L};
+    const int32_t* kf[2] = {m->pt_kf, m->ls_kf};
+    int32_t* loc[2] = {pt_loc, ls_loc};
+    int32_t* pairs[2] = {pt_pairs, ls_pairs};
+    for (int k = 0; k < 2; ++k) {
+        if (n[k] == 0) continue;
+        if (!desc[k] || !X[k] || !kf[k] || !loc[k] || !pairs[k] || !m->T_kf) return GFPL_E_INVALID;
+        if (n[k] >= 2 && misaligned16(desc[k])) return GFPL_E_INVALID;   // rows are read as uint4
+    }
+    if (n[0] == 0 && n[1] == 0) return GFPL_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // per kind: descs [n][32] | idx [n][2] | dist [n][2]; then counts [5]: selected and pairs per kind, the flag
+    uint8_t* dsc[2] = {nullptr, nullptr};
+    int32_t* idx[2] = {nullptr, nullptr};
+    float* dist[2] = {nullptr, nullptr};
+    int* cnt = nullptr;
+    Carver cv;
+    auto layout = [&]() {
+        for (int k = 0; k < 2; ++k) {
+            dsc[k] = cv.take<uint8_t>((size_t)n[k] * 32);
+            idx[k] = cv.take<int32_t>(2 * (size_t)n[k]);
+            dist[k] = cv.take<float>(2 * (size_t)n[k]);
+        }
+        cnt = cv.take<int>(5);
+    };
+    layout();   // sizing pass (base == nullptr)
+    if (cv.off > c->fuse_ws_bytes) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->fuse_ws) (void)hipFree(c->fuse_ws);
+        c->fuse_ws = nullptr;
+        c->fuse_ws_bytes = 0;
+        if (hipMalloc(&c->fuse_ws, cv.off) != hipSuccess) {
+            (void)hipGetLastError();
+            c->fuse_ws = nullptr;
+            return GFPL_E_NOMEM;
+        }
+        c->fuse_ws_bytes = cv.off;
+    }
+    if (!c->fuse_host && hipHostMalloc((void**)&c->fuse_host, 5 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        c->fuse_host = nullptr;
+        return GFPL_E_NOMEM;
+    }
+    for (int k = 0; k < 2; ++k)
+        for (int i = 0; i < 4; ++i)
+            if (!c->fuse_ev[k][i]) HIPCHK(hipEventCreate(&c->fuse_ev[k][i]));
+    cv.off = 0;
+    cv.base = c->fuse_ws;
+    layout();
+    const DevCam cam = devcam(c->cam);
+    hipError_t e = hipMemsetAsync(cnt, 0, 5 * sizeof(int), c->stream);
+    c->fuse_timed[0] = c->fuse_timed[1] = false;
+    bool timed[2] = {false, false};
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        if (n[k] == 0) continue;
+        e = hipEventRecord(c->fuse_ev[k][0], c->stream);
+        if (e != hipSuccess) break;
+        const FuseSelect fs{cam, k, n[k], m->n_kf, X[k], kf[k], m->T_kf, n[k] >= 2 ? desc[k] : nullptr, loc[k], dsc[k], cnt + k,
+                            cnt + 4};
+        e = launch_fuse_select(fs, c->stream);
+        if (n[k] < 2) continue;   // one row has no second neighbour: no pairs
+        if (e == hipSuccess) e = hipEventRecord(c->fuse_ev[k][1], c->stream);
+        if (e == hipSuccess) e = launch_knn2_counts(dsc[k], cnt + k, dsc[k], cnt + k, n[k], 1, idx[k], dist[k], c->stream);
+        if (e == hipSuccess) e = hipEventRecord(c->fuse_ev[k][2], c->stream);
+        const FuseGate fg{k, n[k], cnt + k, loc[k], idx[k], X[k], prm->max_point_point_error, prm->max_point_line_error,
+                          prm->max_dir_line_error, pairs[k], cnt + 2 + k};
+        if (e == hipSuccess) e = launch_fuse_gate(fg, c->stream);
+        if (e == hipSuccess) e = hipEventRecord(c->fuse_ev[k][3], c->stream);
+        timed[k] = e == hipSuccess;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(c->fuse_host, cnt, 5 * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || es != hipSuccess) {
+        std::fprintf(stderr, "gfpl: map_fuse_search failed: %s\n", hipGetErrorString(e != hipSuccess ? e : es));
+        return GFPL_E_HIP;
+    }
+    c->fuse_timed[0] = timed[0];
+    c->fuse_timed[1] = timed[1];
+    *n_pt_loc = c->fuse_host[0];
+    *n_ls_loc = c->fuse_host[1];
+    *n_pt_pairs = c->fuse_host[2];
+    *n_ls_pairs = c->fuse_host[3];
+    return c->fuse_host[4] ? GFPL_E_INVALID : GFPL_OK;   // a keyframe index outside [0, n_kf)
+}
+
+int gfpl_map_fuse_debug_ms(gfpl_ctx* c, int kind, float* ms) {
+    if (!c || !ms || kind < 0 || kind > 1) return GFPL_E_INVALID;
+    if (!c->fuse_timed[kind]) return GFPL_E_STATE;
+    for (int i = 0; i < 3; ++i) HIPCHK(hipEventElapsedTime(ms + i, c->fuse_ev[kind][i], c->fuse_ev[kind][i + 1]));
     return GFPL_OK;
 }
 

@@ -47,6 +47,9 @@ hipError_t launch_knn2(const uint8_t* q, int nq, const uint8_t* t, int nt, int c
                        hipStream_t s);
 hipError_t launch_knn2_batched(const uint8_t* q, const int* nq, const uint8_t* t, const int* nt, int cap, int B,
                                int cell, int32_t* packed, hipStream_t s);
+// launch_knn2 with the two counts on the device (min(*nq, cap) / min(*nt, cap) rows): idx / dist [cap][2]
+hipError_t launch_knn2_counts(const uint8_t* q, const int* nq, const uint8_t* t, const int* nt, int cap, int cell,
+                              int32_t* idx, float* dist, hipStream_t s);
 // radiusMatch rows (count pass, then the rows at row_off) and knn-2 list statistics
 hipError_t launch_radius_count(const uint8_t* q, int nq, const uint8_t* t, int nt, int cell, float radius,
                                int32_t* cnt, hipStream_t s);
@@ -89,6 +92,31 @@ hipError_t launch_kf_gate(const KfGate& g, hipStream_t s);
 hipError_t launch_kf_map_filter(const DevCam& cam, const double* T1, const double* P, int n, int lines,
                                 int32_t* loc, uint8_t* desc_out, const uint8_t* desc_in, int* count, hipStream_t s);
 
+// fuseLandmarksFromLocalMap's candidate search (k_fuse.hip); all pointers device
+struct FuseSelect {
+    DevCam cam;
+    int lines, n, n_kf;
+    const double* X;          // [n][3] point3D or [n][6] line3D
+    const int32_t* kf;        // [n] kf_obs_list[0]
+    const double* T_kf;       // [n_kf][16]
+    const uint8_t* desc_in;   // [n][32], 16-B aligned; null: no descriptor is copied
+    int32_t* loc;             // [n] map row of selected row j
+    uint8_t* desc_out;        // [n][32] the selected rows' descriptors
+    int* count;               // selected rows
+    int* bad_kf;              // set to 1 by a row whose kf is outside [0, n_kf)
+};
+struct FuseGate {
+    int lines, cap;           // cap: the map's rows (what loc / idx / pairs hold)
+    const int* n_sel;         // k_fuse_select's count
+    const int32_t* loc;
+    const int32_t* idx;       // knn-2 of the selected rows against themselves [cap][2]
+    const double* X;
+    double max_pp, max_pl, max_dl;   // maxPointPointError, maxPointLineError, maxDirLineError
+    int32_t* pairs;           // [cap][2] (i, t) over the selected list
+    int* count;
+};
+hipError_t launch_fuse_select(const FuseSelect& a, hipStream_t s);
+hipError_t launch_fuse_gate(const FuseGate& g, hipStream_t s);
 
 // isLoopClosure (k_loop.hip): one candidate pair's knn-2 lists and feature arrays; all pointers device.
 // pi12 / li12 are null for a kind with fewer than two rows on either keyframe (ledger U4).

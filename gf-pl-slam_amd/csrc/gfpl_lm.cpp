@@ -1,7 +1,7 @@
 // gfpl_lm.cpp — host side of the landmark descriptor store (include/gfpl.h): the
 // object that owns the store's device memory and the host mirror of the counts, apply (the planner,
 // one upload of the work items and ops, one launch per lane-group bucket that has work, one
-// synchronisation), gather and read.
+// synchronisation), fuse (the same with the planner of gfpl_lm_fuse_plan.cpp), gather and read.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -10,6 +10,7 @@
 
 #include "../../include/gfpl.h"
 #include "gfpl_kernels.hpp"
+#include "gfpl_lm_fuse_plan.hpp"
 #include "gfpl_lm_plan.hpp"
 
 using namespace gfpl;
@@ -26,6 +27,7 @@ struct gfpl_lmstore {
     std::vector<int32_t> counts;   // the mirror every check runs against
     std::vector<int32_t> slot;     // the planner's scratch, all -1 between calls
     LmPlan plan;
+    LmFusePlan fuse_plan;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the last apply's or gather's kernels (gfpl_lmstore_debug_ms)
     bool timed = false;
     int min_g = 0;                 // GFPL_LM_MIN_LANES as it stood when the store was created
@@ -175,6 +177,68 @@ int gfpl_lmstore_apply(gfpl_lmstore* st, const gfpl_lm_op* ops, int n, const uin
         // describe the device any more, so the store refuses further use
         std::fprintf(stderr, "gfpl: lmstore_apply failed: %s\n", hipGetErrorString(e != hipSuccess ? e : es));
         st->failed = true;
+        return GFPL_E_HIP;
+    }
+    return GFPL_OK;
+}
+
+int gfpl_lmstore_fuse(gfpl_lmstore* st, const gfpl_lm_op* ops, int n, const uint8_t* const* srcs,
+                      const int32_t* src_rows, int n_srcs) {
+    if (!st || n < 0 || (n > 0 && !ops) || n_srcs < 0 || (n_srcs > 0 && (!srcs || !src_rows))) return GFPL_E_INVALID;
+    if (st->failed) return GFPL_E_STATE;
+    if (n == 0) return GFPL_OK;
+    int64_t n_rows = 0;
+    LmFusePlan& pl = st->fuse_plan;
+    const int rc = lm_fuse_plan(ops, n, st->counts.data(), st->lm_cap, st->obs_cap, src_rows, n_srcs, st->min_g, &n_rows,
+                                &pl, st->slot.data());
+    if (rc != GFPL_OK) return rc;
+    auto refuse = [&](int code) {
+        for (const LmFuseTouch& u : pl.touch) st->counts[(size_t)u.lm] = u.count0;   // the mirror as it was
+        return code;
+    };
+    if (n_rows > st->max_ops) return refuse(GFPL_E_CAPACITY);
+    // every gained row as an ADD from its origin: a source row, or a row of the store below its
+    // landmark's count before the call, which no work item of this call writes
+    const LmStoreDev sd = dev_of(st);
+    const LmWorkMem hm(st->stage, st->max_ops);
+    const int n_work = (int)pl.work.size();
+    for (int w = 0; w < n_work; ++w) {
+        const LmFuseTouch& u = pl.touch[(size_t)pl.work_touch[(size_t)w]];
+        LmOpDev* o = hm.ops + pl.work[(size_t)w].op0;
+        if (u.freed) {
+            *o = LmOpDev{nullptr, GFPL_LM_FREE, 0};
+            continue;
+        }
+        for (const LmOrigin& g : u.gained) {
+            const uint8_t* p;
+            if (g.src >= 0) {
+                p = srcs[g.src];
+                if (!p || ((uintptr_t)p & 15) != 0) return refuse(GFPL_E_INVALID);
+                p += 32 * (size_t)g.row;
+            } else {
+                p = sd.rows + ((size_t)(-1 - g.src) * st->obs_cap + (size_t)g.row) * 32;
+            }
+            *o++ = LmOpDev{p, GFPL_LM_ADD, 0};
+        }
+    }
+    std::memcpy(hm.work, pl.work.data(), (size_t)n_work * sizeof(LmWork));
+
+    if (hipSetDevice(gfpl_ctx_device(st->ctx)) != hipSuccess) return refuse(GFPL_E_HIP);   // nothing was enqueued
+    hipStream_t s = stream_of(st->ctx);
+    const LmWorkMem dm(st->base + st->store_bytes, st->max_ops);
+    hipError_t e = hipMemcpyAsync(dm.work, hm.work, (size_t)n_work * sizeof(LmWork), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(dm.ops, hm.ops, (size_t)pl.n_dev_ops * sizeof(LmOpDev), hipMemcpyHostToDevice, s);
+    st->timed = false;
+    if (e == hipSuccess) e = hipEventRecord(st->ev0, s);
+    for (int b = 0; b < LM_BUCKETS && e == hipSuccess; ++b)
+        e = launch_lm_apply(sd, dm.work, dm.ops, pl.bucket_start[b], pl.bucket_start[b + 1] - pl.bucket_start[b], b, s);
+    if (e == hipSuccess) e = hipEventRecord(st->ev1, s);
+    const hipError_t es = hipStreamSynchronize(s);   // also on an error path: the staging is still in use
+    st->timed = e == hipSuccess && es == hipSuccess;
+    if (e != hipSuccess || es != hipSuccess) {
+        std::fprintf(stderr, "gfpl: lmstore_fuse failed: %s\n", hipGetErrorString(e != hipSuccess ? e : es));
+        st->failed = true;   // as in apply: neither the mirror nor the counts before the call describe the device
         return GFPL_E_HIP;
     }
     return GFPL_OK;

@@ -154,6 +154,12 @@ hipError_t launch_knn2_batched(const uint8_t* q, const int* nq, const uint8_t* t
     return cell == 2 ? launch_knn2_as<2>(a, cap, cap, B, s) : launch_knn2_as<1>(a, cap, cap, B, s);
 }
 
+hipError_t launch_knn2_counts(const uint8_t* q, const int* nq, const uint8_t* t, const int* nt, int cap, int cell,
+                              int32_t* idx, float* dist, hipStream_t s) {
+    const Knn2Args a{q, t, nq, nt, 0, 0, cap, idx, dist, nullptr};
+    return cell == 2 ? launch_knn2_as<2>(a, cap, cap, 1, s) : launch_knn2_as<1>(a, cap, cap, 1, s);
+}
+
 // ---------------------------------------------------------------- radius --
 template <int CELL>
 __global__ void __launch_bounds__(256) k_radius_count(const uint8_t* q, int nq, const uint8_t* t, int nt,

@@ -436,6 +436,47 @@ class MapView:
             setattr(self.s, k, _ptr(a) if (device is not None or a.size) else 0)
 
 
+class FuseParams(C.Structure):
+    """gfpl_fuse_params: Config::maxPointPointError / maxPointLineError / maxDirLineError
+    (src/config.cpp:46-48); FuseParams.default() fills the reference's values."""
+    _fields_ = [("max_point_point_error", C.c_double), ("max_point_line_error", C.c_double),
+                ("max_dir_line_error", C.c_double)]
+
+    @classmethod
+    def default(cls, **over) -> "FuseParams":
+        p = cls()
+        hiplib().gfpl_default_fuse_params(C.byref(p))
+        for k, v in over.items():
+            setattr(p, k, v)
+        return p
+
+
+class FuseMapStruct(C.Structure):
+    """gfpl_fuse_map"""
+    _fields_ = [("map", MapViewStruct), ("pt_kf", _vp), ("ls_kf", _vp), ("n_kf", C.c_int), ("T_kf", _vp)]
+
+
+class FuseMap:
+    """gfpl_fuse_map: the local landmarks fuseLandmarksFromLocalMap searches (med_desc row 0, point3D /
+    line3D, kf_obs_list[0]) and the keyframes' T_kf_w [n_kf][16], copied to `device` (torch)."""
+
+    def __init__(self, pdesc, P, pt_kf, ldesc, L, ls_kf, T_kf, device="cuda"):
+        import torch
+        self.view = MapView(pdesc, P, ldesc, L, device=device)
+        self.s = FuseMapStruct()
+        self.s.map = self.view.s
+        T = np.ascontiguousarray(T_kf, np.float64).reshape(-1, 16)
+        self.s.n_kf = len(T)
+        self.keep = {}
+        for k, a in (("pt_kf", np.ascontiguousarray(pt_kf, np.int32).reshape(-1)),
+                     ("ls_kf", np.ascontiguousarray(ls_kf, np.int32).reshape(-1)), ("T_kf", T)):
+            a = torch.from_numpy(a.copy()).to(device) if a.size else torch.zeros(1, device=device)
+            self.keep[k] = a
+            setattr(self.s, k, _ptr(a))
+        if len(self.keep["pt_kf"]) < self.s.map.n_pt or len(self.keep["ls_kf"]) < self.s.map.n_ls:
+            raise ValueError("FuseMap: one keyframe index per landmark")
+
+
 class OrbParams(C.Structure):
     """gfpl_orb_params: ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST)."""
     _fields_ = [("nfeatures", C.c_int), ("scale_factor", C.c_float), ("nlevels", C.c_int),
@@ -592,6 +633,9 @@ def hiplib() -> C.CDLL:
             "gfpl_kf_common_matches": ([P, P, P, P, P, P, P], C.c_int),
             "gfpl_kf_local_map_matches": ([P, P, P, C.c_double, C.c_double, P, P, P, P], C.c_int),
             "gfpl_default_loop_params": ([P], None),
+            "gfpl_default_fuse_params": ([P], None),
+            "gfpl_map_fuse_search": ([P, P, P, P, P, P, P, P, P, P, P], C.c_int),
+            "gfpl_map_fuse_debug_ms": ([P, C.c_int, P], C.c_int),
             "gfpl_kf_loop_closure": ([P, P, P, C.c_int, P, C.c_int, C.c_int, P, P, P, P, P], C.c_int),
             "gfpl_vocab_create": ([P, P, P], C.c_int),
             "gfpl_vocab_destroy": ([P], C.c_int),
@@ -669,6 +713,8 @@ def hiplib() -> C.CDLL:
             "gfpl_lmstore_bytes": ([P], C.c_int64),
             "gfpl_lm_ops_check": ([P, C.c_int, P, C.c_int, C.c_int, P, C.c_int], C.c_int),
             "gfpl_lmstore_apply": ([P, P, C.c_int, P, P, C.c_int], C.c_int),
+            "gfpl_lm_fuse_check": ([P, C.c_int, P, C.c_int, C.c_int, P, C.c_int, P], C.c_int),
+            "gfpl_lmstore_fuse": ([P, P, C.c_int, P, P, C.c_int], C.c_int),
             "gfpl_lmstore_gather": ([P, P, C.c_int, P, P], C.c_int),
             "gfpl_lmstore_read": ([P, C.c_int, P, P, P, P], C.c_int),
             "gfpl_lmstore_debug_ms": ([P, P], C.c_int),
@@ -1124,6 +1170,41 @@ class Context:
                                                _ptr(lp), C.byref(nls)), "kf_local_map_matches")
         return (pp[: 2 * npt.value].cpu().numpy().reshape(-1, 2),
                 lp[: 2 * nls.value].cpu().numpy().reshape(-1, 2))
+
+    def fuseSearch_rc(self, fuse_map: "FuseMap", params: Optional["FuseParams"] = None):
+        """gfpl_map_fuse_search: (return code, dict of pt_loc, pt_pairs, ls_loc, ls_pairs as numpy arrays)."""
+        import torch
+        s = fuse_map.s
+        dev = torch.device("cuda", torch.cuda.current_device())
+        out = {k: torch.zeros(w * max(n, 1), dtype=torch.int32, device=dev)
+               for k, w, n in (("pt_loc", 1, s.map.n_pt), ("pt_pairs", 2, s.map.n_pt), ("ls_loc", 1, s.map.n_ls),
+                               ("ls_pairs", 2, s.map.n_ls))}
+        cnt = {k: C.c_int(0) for k in out}
+        prm = params or FuseParams.default()
+        torch.cuda.synchronize()
+        rc = self.L.gfpl_map_fuse_search(self.h, C.byref(s), C.byref(prm), _ptr(out["pt_loc"]), C.byref(cnt["pt_loc"]),
+                                         _ptr(out["pt_pairs"]), C.byref(cnt["pt_pairs"]), _ptr(out["ls_loc"]),
+                                         C.byref(cnt["ls_loc"]), _ptr(out["ls_pairs"]), C.byref(cnt["ls_pairs"]))
+        res = {}
+        for k, t in out.items():
+            w = 2 if k.endswith("pairs") else 1
+            a = t[: w * cnt[k].value].cpu().numpy()
+            res[k] = a.reshape(-1, 2) if w == 2 else a
+        return rc, res
+
+    def fuseSearch(self, fuse_map: "FuseMap", params: Optional["FuseParams"] = None) -> dict:
+        """The candidate search of fuseLandmarksFromLocalMap (src/mapHandler.cpp:859-1056): pt_loc / ls_loc
+        (map row of every selected row) and pt_pairs / ls_pairs ((i, t) over the selected list, the
+        reference's map_local_*_to_fuse) in the reference's order."""
+        rc, res = self.fuseSearch_rc(fuse_map, params)
+        check(rc, "map_fuse_search")
+        return res
+
+    def fuseSearch_device_ms(self, kind: int):
+        """gfpl_map_fuse_debug_ms: (select, knn-2, gate) device milliseconds of the last fuseSearch, per kind."""
+        ms = (C.c_float * 3)()
+        check(self.L.gfpl_map_fuse_debug_ms(self.h, int(kind), ms), "map_fuse_debug_ms")
+        return [float(v) for v in ms]
 
     def isLoopClosure(self, kf0_views, kf1_views, params: Optional[LoopParams] = None):
         """MapHandler::isLoopClosure (src/mapHandler.cpp:3078-3545) for a batch of candidate pairs
@@ -1677,6 +1758,7 @@ class PoseGraph:
 
 LM_MAX_OBS = 64
 LM_ADD, LM_ERASE_OBS, LM_FREE = 0, 1, 2
+LM_APPEND_LM = 3   # fuse / lm_fuse_check only
 
 
 def _lm_ops(ops) -> np.ndarray:
@@ -1694,6 +1776,18 @@ def lm_ops_check(ops, counts, obs_cap: int, src_rows):
     rc = hiplib().gfpl_lm_ops_check(_ptr(o), len(o), _ptr(cnt), len(cnt), int(obs_cap),
                                     _ptr(rows) if len(rows) else 0, len(rows))
     return rc, cnt
+
+
+def lm_fuse_check(ops, counts, obs_cap: int, src_rows):
+    """gfpl_lm_fuse_check (host only): (return code, counts after, n_rows) of a fuse list, the ops
+    run one after another.  A refused list returns the counts unchanged and n_rows 0."""
+    o = _lm_ops(ops)
+    cnt = np.array(counts, np.int32)
+    rows = np.ascontiguousarray(src_rows, np.int32).reshape(-1)
+    n_rows = C.c_int64(-1)
+    rc = hiplib().gfpl_lm_fuse_check(_ptr(o), len(o), _ptr(cnt), len(cnt), int(obs_cap),
+                                     _ptr(rows) if len(rows) else 0, len(rows), C.byref(n_rows))
+    return rc, cnt, int(n_rows.value)
 
 
 class LandmarkStore:
@@ -1723,6 +1817,21 @@ class LandmarkStore:
 
     def apply(self, ops, srcs, src_rows=None) -> None:
         check(self.apply_rc(ops, srcs, src_rows), "lmstore_apply")
+
+    def fuse_rc(self, ops, srcs, src_rows=None, src_ptrs=None) -> int:
+        """gfpl_lmstore_fuse's return code: ADD, FREE and LM_APPEND_LM ops run one after another over
+        the whole list (MapHandler::loopClosureFuseLandmarks' merges, without a row leaving the device)."""
+        import torch
+        o = _lm_ops(ops)
+        srcs = list(srcs)
+        rows = np.array([int(s.shape[0]) for s in srcs] if src_rows is None else src_rows, np.int32)
+        ptrs = (C.c_void_p * max(len(srcs), 1))(*([_ptr(s) for s in srcs] if src_ptrs is None else src_ptrs))
+        torch.cuda.synchronize()
+        return self.L.gfpl_lmstore_fuse(self.h, _ptr(o), len(o), ptrs if len(srcs) else None,
+                                        _ptr(rows) if len(srcs) else 0, len(srcs))
+
+    def fuse(self, ops, srcs, src_rows=None) -> None:
+        check(self.fuse_rc(ops, srcs, src_rows), "lmstore_fuse")
 
     def gather(self, ids, with_idx: bool = False):
         """Device tensor [n][32] of the ids' median rows (a MapView's pdesc / ldesc); with_idx: also

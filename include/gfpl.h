@@ -788,6 +788,62 @@ int  gfpl_lmstore_read(gfpl_lmstore* st, int lm, int32_t* count, int32_t* med_id
  * kernel of the store's last apply or gather that launched any; GFPL_E_STATE when there is none. */
 int  gfpl_lmstore_debug_ms(gfpl_lmstore* st, float* ms);
 
+/* Ops that cross landmarks: what MapHandler::loopClosureFuseLandmarks (src/mapHandler.cpp:4425 ff.)
+ * does to desc_list, without a descriptor leaving the device (DESIGN.md §4i "fuse").             */
+#define GFPL_LM_APPEND_LM 3   /* gfpl_lmstore_fuse / gfpl_lm_fuse_check only: desc_list of `lm` += desc_list of landmark
+                                 `arg` as it stands at this op; `src` is not read.  apply / ops_check keep refusing it. */
+/* Host only, no device: gfpl_lm_ops_check for a fuse list.  The ops run one after another over the
+ * whole list, and the first that fails decides.  GFPL_E_INVALID: everything gfpl_lm_ops_check
+ * refuses for ADD / FREE, an append whose arg is outside [0, lm_cap) or equals lm or has a count
+ * outside [0, obs_cap], an append from or to a landmark whose list is empty at that op, any op that
+ * names (as lm or arg) a landmark that an earlier FREE of the list emptied.  GFPL_E_UNSUPPORTED:
+ * GFPL_LM_ERASE_OBS.  GFPL_E_CAPACITY: a list beyond obs_cap.  n_rows (may be NULL) receives 1 per
+ * ADD or FREE plus the source's length per append, 0 for a refused list.                        */
+int  gfpl_lm_fuse_check(const gfpl_lm_op* ops, int n, int32_t* counts /*[lm_cap] in: before, out: after*/, int lm_cap,
+                        int obs_cap, const int32_t* src_rows, int n_srcs, int64_t* n_rows /*may be NULL*/);
+/* Runs the ops one after another in array order over the whole list (apply orders them per landmark
+ * only).  Afterwards every landmark named as an op's lm has the count / med_idx / med_desc of
+ * updateAverageDescDir over its final list; a landmark named only as arg is unchanged.  The order of
+ * a list is kept: an append adds the source's observations in their order.  Runs gfpl_lm_fuse_check
+ * against the store's counts before any device work, with the same codes; GFPL_E_CAPACITY also for
+ * n_rows > max_ops, GFPL_E_INVALID also for an ADD from a NULL or misaligned srcs[src]; GFPL_E_STATE
+ * and GFPL_E_HIP as for apply.  A refused call changes nothing.  Synchronises once.              */
+int  gfpl_lmstore_fuse(gfpl_lmstore* st, const gfpl_lm_op* ops /*HOST*/, int n,
+                       const uint8_t* const* srcs /*HOST array of DEVICE [rows][32], 16-B aligned*/,
+                       const int32_t* src_rows, int n_srcs);
+
+/* The candidate search of MapHandler::fuseLandmarksFromLocalMap (src/mapHandler.cpp:859-1056; k_fuse.hip,
+ * DESIGN.md §4l, ledger FU1-FU11); the list walk that follows it stays the caller's.
+ * Per kind: (1) the rows whose projection under T = T_kf[kf] (taken as written: the reference names it
+ * Twf and does not invert it) lies strictly inside the image with Pf.z > 0, lines with both endpoints,
+ * are compacted in map order: loc[j] is the map row of selected row j; (2) with more than one selected
+ * row, knn-2 NORM_HAMMING of the selected median rows against themselves (the tie rule of
+ * gfpl_knn2_hamming) and for row i its SECOND neighbour t (lmatches_12[i][1]), skipped when t == i;
+ * (3) points: |P_t - P_i| < max_point_point_error; lines: |d1 - d2| < max_dir_line_error and both
+ * endpoints of one line within max_point_line_error of the other, which line deciding d1.norm() >
+ * d2.norm() as written; all comparisons strict, NaN fails; (4) pairs (i, t) over the selected list in
+ * ascending i (map_local_*_to_fuse); both (i, t) and (t, i) may appear.  A kind with n == 0 or fewer than
+ * two selected rows yields no pairs.  Counts to the host; synchronises once.  GFPL_E_INVALID: a NULL
+ * pointer, a negative count, a misaligned descriptor pointer of a kind with two or more rows, a context
+ * without a camera, and (after the device work, outputs then unspecified) a pt_kf / ls_kf entry outside
+ * [0, n_kf): such a row is never used as an index.  GFPL_E_NOMEM when the context's workspace cannot grow. */
+typedef struct gfpl_fuse_params { double max_point_point_error, max_point_line_error, max_dir_line_error; } gfpl_fuse_params;
+void gfpl_default_fuse_params(gfpl_fuse_params* prm);   /* 0.1, 0.1, 0.1 (src/config.cpp:46-48) */
+typedef struct gfpl_fuse_map {
+    gfpl_map_view  map;      /* the caller's `!= NULL && local` landmarks in map order (:869-874, :961-966); pdesc / ldesc =
+                                med rows (gfpl_lmstore_gather), P = point3D, L = line3D                                   */
+    const int32_t* pt_kf;    /* DEVICE [n_pt]  kf_obs_list[0]                                                           */
+    const int32_t* ls_kf;    /* DEVICE [n_ls]                                                                           */
+    int            n_kf;
+    const double*  T_kf;     /* DEVICE [n_kf][16]  T_kf_w (the layout of gfpl_pgo_problem.T_kf)                          */
+} gfpl_fuse_map;
+int  gfpl_map_fuse_search(gfpl_ctx* ctx, const gfpl_fuse_map* m, const gfpl_fuse_params* prm,
+                          int32_t* pt_loc /*DEVICE [n_pt]*/, int* n_pt_loc, int32_t* pt_pairs /*DEVICE [n_pt][2]*/, int* n_pt_pairs,
+                          int32_t* ls_loc /*DEVICE [n_ls]*/, int* n_ls_loc, int32_t* ls_pairs /*DEVICE [n_ls][2]*/, int* n_ls_pairs);
+/* Instrumentation (tools/bench_lm_fuse.py): device milliseconds of the last search's select, knn-2 and
+ * gate launches of kind 0 (points) or 1 (lines); GFPL_E_STATE when that kind launched fewer than all three. */
+int  gfpl_map_fuse_debug_ms(gfpl_ctx* ctx, int kind, float* ms /*HOST [3]*/);
+
 /* ------------------------------------- loop-closure candidate search ----- */
 /* DBoW2 as MapHandler uses it (insertKFBowVectorP / L / PL, src/mapHandler.cpp:2865-3000, and
  * lookForLoopCandidates, :3002-3076): TemplatedVocabulary<FORB>::transform and L1Scoring::score
@@ -1037,8 +1093,10 @@ int  gfpl_gba_debug_system(gfpl_gba* gba, int i, int iteration, double* U, doubl
  * keyframe pose and every landmark that hangs on it (k_pgo_correct).  The graph (vertices, flags,
  * edge order), the measurements, the start poses and the map correction are the reference's.  The
  * objective and the iteration are pinned by DESIGN.md §4j (ledger PG1-PG8), not by g2o, which the
- * reference tree does not contain.  Not here: loopClosureFuseLandmarks, per-edge information
- * matrices (the reference passes identity), globalBundleAdjustment.                             */
+ * reference tree does not contain.  loopClosureFuseLandmarks, which follows the solve, has its
+ * descriptor half in gfpl_lmstore_fuse (the list walk stays the caller's).
+ * Not here: per-edge information matrices (the reference passes identity); globalBundleAdjustment
+ * is gfpl_gba_solve.                                                                            */
 #define GFPL_PGO_COV 0          /* loopClosureOptimizationCovGraphG2O */
 #define GFPL_PGO_ESS 1          /* loopClosureOptimizationEssGraphG2O */
 typedef struct gfpl_pgo gfpl_pgo;
