@@ -751,6 +751,7 @@ struct gfplo_handler {
     double T_prevKF[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     double cov_prevKF_currF[36] = {0};
     int need_new_kf = 0;
+    int64_t cut_steps = 0;   // lineCut: iterations of the search loop of the last call
 
     // needNewKF (src/stereoFrameHandler.cpp:2309-2349)
     bool needNewKF() {
@@ -1324,6 +1325,7 @@ struct gfplo_handler {
 
     // estimateProjUncertainty_submodular (src/stereoFrameHandler.cpp:1618-1764)
     void lineCut() {
+        cut_steps = 0;
         if (matched_ls.empty()) return;
         const double s = cfg.cut_step;
         const double nb[8][2] = {{s, 0}, {-s, 0}, {0, s}, {0, -s}, {s, s}, {s, -s}, {-s, s}, {-s, -s}};
@@ -1371,6 +1373,7 @@ struct gfplo_handler {
                 double cand[2] = {0, 0};
                 double cand_info[36];
                 double metric_init = metric_back;
+                ++cut_steps;
                 CUT_STAT(g_cut_stats[1]++);   // steps
 #ifdef GFPL_ORACLE_CUT_STATS
                 double mv[8];
@@ -1823,6 +1826,7 @@ int gfplo_cross_lines(gfplo_handler* h) {
     return 0;
 }
 int gfplo_line_cut(gfplo_handler* h) { if (!h->prev || !h->curr) return GFPL_E_STATE; h->lineCut(); return 0; }
+int gfplo_line_cut_steps(gfplo_handler* h, int64_t* out) { if (!out) return GFPL_E_INVALID; *out = h->cut_steps; return 0; }
 
 int gfplo_insert_stereo_pair(gfplo_handler* h, const gfpl_frames* in, int seq) {
     int e = gfplo_begin_frame(h, in, seq);

@@ -116,6 +116,8 @@ int gfplo_line_uncertainty(gfplo_handler* h);
 int gfplo_cross_points(gfplo_handler* h);   /* includes predictFramePose */
 int gfplo_cross_lines(gfplo_handler* h);
 int gfplo_line_cut(gfplo_handler* h);
+/* search steps (iterations of the while loop, :1681) of the last gfplo_line_cut */
+int gfplo_line_cut_steps(gfplo_handler* h, int64_t* out);
 
 int gfplo_read_frame(gfplo_handler* h, int which, gfpl_frame_host* out);
 int gfplo_write_frame(gfplo_handler* h, int which, const gfpl_frame_host* in);

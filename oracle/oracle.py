@@ -38,6 +38,7 @@ def lib() -> C.CDLL:
             getattr(L, n).argtypes = [P, C.c_int, P]; getattr(L, n).restype = C.c_int
         for n in ["gfplo_read_track", "gfplo_write_track", "gfplo_need_new_kf", "gfplo_read_kf_state"]:
             getattr(L, n).argtypes = [P, P]; getattr(L, n).restype = C.c_int
+        L.gfplo_line_cut_steps.argtypes = [P, P]; L.gfplo_line_cut_steps.restype = C.c_int
         L.gfplo_curr_frame_is_kf.argtypes = [P]; L.gfplo_curr_frame_is_kf.restype = C.c_int
         L.gfplo_det6.argtypes = [P]; L.gfplo_det6.restype = C.c_double
         L.gfplo_optimize_pose_ini.argtypes = [P, P]; L.gfplo_optimize_pose_ini.restype = C.c_int
@@ -131,6 +132,12 @@ class OracleHandler:
 
     def estimateProjUncertainty_submodular(self):
         self._c(self.L.gfplo_line_cut(self.h), "line_cut")
+
+    def line_cut_steps(self) -> int:
+        """Search steps (iterations of the while loop) of the last estimateProjUncertainty_submodular."""
+        n = C.c_int64()
+        self._c(self.L.gfplo_line_cut_steps(self.h, C.byref(n)), "line_cut_steps")
+        return n.value
 
     def read_frame(self, which: int) -> gfpl.FrameHost:
         fh = gfpl.FrameHost(self.kp_cap, self.kl_cap)
