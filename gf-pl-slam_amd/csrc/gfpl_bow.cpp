@@ -3,16 +3,10 @@
 // score calls around k_bow.hip, the keyframe database (insertKFBowVectorP / L / PL,
 // src/mapHandler.cpp:2865-3000) and the two pure host functions, vector_stdv of a keyframe's
 // features and lookForLoopCandidates (:3002-3076).
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <vector>
 
-#include "../../include/gfpl.h"
-#include "gfpl_kernels.hpp"
+#include "gfpl_host.hpp"
 
 using namespace gfpl;
 
@@ -40,17 +34,6 @@ struct gfpl_bowdb {
 };
 
 namespace {
-
-#define BOW_HIPCHK(x)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (x);                                                            \
-        if (e_ != hipSuccess) {                                                         \
-            std::fprintf(stderr, "gfpl: %s failed: %s\n", #x, hipGetErrorString(e_));   \
-            return GFPL_E_HIP;                                                          \
-        }                                                                               \
-    } while (0)
-
-hipStream_t stream_of(const gfpl_ctx* c) { return (hipStream_t)gfpl_ctx_stream(c); }
 
 // the scratch of a transform call over n sets of capacity cap
 struct BowScratch {
@@ -185,7 +168,7 @@ int gfpl_vocab_create(gfpl_ctx* ctx, const gfpl_vocab_desc* d, gfpl_vocab** out)
         H.rank_weight[r] = w;
         H.node[k].key = w > 0 ? r : BOW_STOP;   // "if(w > 0)": also drops NaN
     }
-    BOW_HIPCHK(hipSetDevice(gfpl_ctx_device(ctx)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(ctx)));
     char* base = nullptr;
     if (hipMalloc(&base, size.bytes) != hipSuccess) {
         (void)hipGetLastError();
@@ -230,11 +213,11 @@ int gfpl_bow_transform(gfpl_ctx* c, const gfpl_vocab* voc, int n, const uint8_t*
     if (max_count > cap) return GFPL_E_CAPACITY;
     if (cap > GFPL_BOW_MAX_CAP || n > 65535) return GFPL_E_UNSUPPORTED;
     if (max_count > 0 && (!word_ids || !values)) return GFPL_E_INVALID;
-    BOW_HIPCHK(hipSetDevice(voc->device));
+    GFPL_HIPCHK(hipSetDevice(voc->device));
     hipStream_t s = stream_of(c);
     const BowScratch size(nullptr, n, cap);
     char* scr = nullptr;
-    BOW_HIPCHK(hipMalloc(&scr, size.bytes));
+    GFPL_HIPCHK(hipMalloc(&scr, size.bytes));
     const BowScratch S(scr, n, cap);
     std::vector<BowSet> hs((size_t)n);
     for (int i = 0; i < n; ++i) hs[i] = BowSet{desc_ptrs[i], counts[i], 0};
@@ -260,10 +243,10 @@ int gfpl_bow_score(gfpl_ctx* c, const gfpl_bow_vec* a, const gfpl_bow_vec* b, in
         if (b[i].count > 0 && (!b[i].ids || !b[i].values)) return GFPL_E_INVALID;
         hp[i] = BowPair{a[i].ids, a[i].values, b[i].ids, b[i].values, a[i].count, b[i].count};
     }
-    BOW_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
     hipStream_t s = stream_of(c);
     BowPair* dp = nullptr;
-    BOW_HIPCHK(hipMalloc(&dp, (size_t)n_pairs * sizeof(BowPair)));
+    GFPL_HIPCHK(hipMalloc(&dp, (size_t)n_pairs * sizeof(BowPair)));
     hipError_t e = hipMemcpyAsync(dp, hp.data(), (size_t)n_pairs * sizeof(BowPair), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = launch_bow_score(dp, n_pairs, scores, s);
     hipError_t es = hipStreamSynchronize(s);
@@ -293,7 +276,7 @@ int gfpl_bowdb_create(gfpl_ctx* c, const gfpl_vocab* voc_p, const gfpl_vocab* vo
     if ((has_p && voc_p->device != gfpl_ctx_device(c)) || (has_l && voc_l->device != gfpl_ctx_device(c)))
         return GFPL_E_INVALID;
     if ((has_p && pt_cap > GFPL_BOW_MAX_CAP) || (has_l && ls_cap > GFPL_BOW_MAX_CAP)) return GFPL_E_UNSUPPORTED;
-    BOW_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
     const BowDbMem size(nullptr, kf_cap, pt_cap, ls_cap, has_p, has_l);
     char* base = nullptr;
     if (hipMalloc(&base, size.bytes) != hipSuccess) {
@@ -343,7 +326,7 @@ int gfpl_bowdb_insert(gfpl_bowdb* db, int kf_idx, const gfpl_kf_view* kf, const 
         if (rows[k] < 0 || (rows[k] > 0 && (!desc[k] || ((uintptr_t)desc[k] & 15)))) return GFPL_E_INVALID;
         if (rows[k] > db->cap[k]) return GFPL_E_CAPACITY;
     }
-    BOW_HIPCHK(hipSetDevice(gfpl_ctx_device(db->ctx)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(db->ctx)));
     hipStream_t s = stream_of(db->ctx);
     // the keyframe's BowVectors, written into its slots (kf->descDBoW_P / _L)
     BowSet hs[2] = {{desc[0], rows[0], 0}, {desc[1], rows[1], 0}};
@@ -422,11 +405,11 @@ int gfpl_bowdb_vector(const gfpl_bowdb* db, int kind, int kf_idx, gfpl_bow_vec* 
     out->values = db->vals[kind] + o;
     out->count = db->count[kind][kf_idx];
     if ((ids_host || values_host) && out->count > 0) {
-        BOW_HIPCHK(hipSetDevice(gfpl_ctx_device(db->ctx)));
-        BOW_HIPCHK(hipStreamSynchronize(stream_of(db->ctx)));
-        if (ids_host) BOW_HIPCHK(hipMemcpy(ids_host, out->ids, (size_t)out->count * sizeof(int32_t), hipMemcpyDeviceToHost));
+        GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(db->ctx)));
+        GFPL_HIPCHK(hipStreamSynchronize(stream_of(db->ctx)));
+        if (ids_host) GFPL_HIPCHK(hipMemcpy(ids_host, out->ids, (size_t)out->count * sizeof(int32_t), hipMemcpyDeviceToHost));
         if (values_host)
-            BOW_HIPCHK(hipMemcpy(values_host, out->values, (size_t)out->count * sizeof(double), hipMemcpyDeviceToHost));
+            GFPL_HIPCHK(hipMemcpy(values_host, out->values, (size_t)out->count * sizeof(double), hipMemcpyDeviceToHost));
     }
     return GFPL_OK;
 }

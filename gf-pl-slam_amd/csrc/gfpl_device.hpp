@@ -236,6 +236,7 @@ GFPL_DEV double det_acos(double x) {
 }
 
 GFPL_DEV double ref_max(double a, double b) { return (a < b) ? b : a; }
+GFPL_DEV bool ref_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and inf
 
 // ------------------------------------------------------------- Hamming
 // OpenCV normHamming, cellSize 1 (NORM_HAMMING) or 2 (NORM_HAMMING2), on

@@ -3,15 +3,8 @@
 // (every problem is checked and planned on the host first; one upload of the planner's index arrays
 // per problem, every launch of every iteration enqueued, one copy of the results, one
 // synchronisation) and the test hook that reads a problem's last evaluated system back.
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
-#include "../../include/gfpl.h"
 #include "gfpl_gba_plan.hpp"
-#include "gfpl_kernels.hpp"
+#include "gfpl_host.hpp"
 
 using namespace gfpl;
 
@@ -32,19 +25,6 @@ struct gfpl_gba {
 };
 
 namespace {
-
-#define GBA_HIPCHK(x)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (x);                                                            \
-        if (e_ != hipSuccess) {                                                         \
-            std::fprintf(stderr, "gfpl: %s failed: %s\n", #x, hipGetErrorString(e_));   \
-            return GFPL_E_HIP;                                                          \
-        }                                                                               \
-    } while (0)
-
-hipStream_t stream_of(const gfpl_ctx* c) { return (hipStream_t)gfpl_ctx_stream(c); }
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int check_counts(const gfpl_gba_counts& c) {
     const gfpl_lba_counts& n = c.n;
@@ -69,11 +49,6 @@ bool within(const gfpl_gba_counts& c, const gfpl_gba_counts& caps) {
     return c.n.n_kf <= caps.n.n_kf && c.n.n_pt <= caps.n.n_pt && c.n.n_ls <= caps.n.n_ls && c.n.n_pt_obs <= caps.n.n_pt_obs &&
            c.n.n_ls_obs <= caps.n.n_ls_obs && c.n_pt_pairs <= caps.n_pt_pairs && c.n_ls_pairs <= caps.n_ls_pairs &&
            c.n_terms <= caps.n_terms;
-}
-
-template <typename T>
-void put(T* dst, const std::vector<T>& src) {
-    if (!src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(T));
 }
 
 }  // namespace
@@ -103,7 +78,7 @@ int gfpl_gba_create(gfpl_ctx* c, const gfpl_gba_counts* caps, int max_problems, 
     const int rc = check_counts(*caps);
     if (rc != GFPL_OK) return rc;
     if (!gfpl_ctx_camera(c)) return GFPL_E_STATE;
-    GBA_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
     gfpl_gba* l = new gfpl_gba();
     l->ctx = c;
     l->caps = *caps;
@@ -155,9 +130,7 @@ int gfpl_gba_solve(gfpl_gba* l, const gfpl_lba_problem* problems, int n, const g
         const gfpl_lba_problem& p = problems[i];
         const int rc = gba_plan(&p, &plans[(size_t)i]);
         if (rc != GFPL_OK) return rc;
-        if (!p.x_kf || !p.T_kf || (p.n.n_fix > 0 && !p.T_fix)) return GFPL_E_INVALID;
-        if (p.n.n_pt > 0 && (!p.pt || !p.pt_obs || !p.pt_sigma)) return GFPL_E_INVALID;
-        if (p.n.n_ls > 0 && (!p.ls || !p.ls_obs || !p.ls_sigma)) return GFPL_E_INVALID;
+        if (!ba_problem_pointers_ok(p)) return GFPL_E_INVALID;
     }
     if (n > l->max_problems) return GFPL_E_CAPACITY;
     for (int i = 0; i < n; ++i)
@@ -165,7 +138,7 @@ int gfpl_gba_solve(gfpl_gba* l, const gfpl_lba_problem* problems, int n, const g
     if (n == 0) return GFPL_OK;
     const gfpl_camera* cam = gfpl_ctx_camera(l->ctx);
     if (!cam) return GFPL_E_STATE;
-    GBA_HIPCHK(hipSetDevice(gfpl_ctx_device(l->ctx)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(l->ctx)));
     hipStream_t s = stream_of(l->ctx);
 
     l->last.assign((size_t)n, GbaProb{});
@@ -184,16 +157,14 @@ int gfpl_gba_solve(gfpl_gba* l, const gfpl_lba_problem* problems, int n, const g
         if (e != hipSuccess) break;
         GbaArgs a;
         std::memset(&a, 0, sizeof a);
-        a.cam.fx = cam->fx; a.cam.fy = cam->fy; a.cam.cx = cam->cx; a.cam.cy = cam->cy; a.cam.b = cam->b;
+        a.cam = dev_cam(cam);
         a.homog_th = gfpl_ctx_config(l->ctx)->homog_th;
         a.prm = *prm;
         a.rules = GBA_RULES_REFERENCE;
         a.out = l->d_res + i;
         GbaProb& q = a.pr;
         q.n = g.n;
-        q.x_kf = p.x_kf; q.T_kf = p.T_kf; q.T_fix = p.T_fix; q.pt = p.pt; q.ls = p.ls;
-        q.pt_obs = p.pt_obs; q.pt_sigma = p.pt_sigma; q.ls_obs = p.ls_obs; q.ls_sigma = p.ls_sigma;
-        q.x_out = p.x_out;
+        ba_fill_prob(q, p);
         q.lm_start = di.lm_start; q.obs_lm = di.obs_lm; q.obs_kf = di.obs_kf; q.obs_pair = di.obs_pair;
         q.pair_start = di.pair_start; q.pair_kf = di.pair_kf; q.kf_start = di.kf_start; q.kf_obs = di.kf_obs;
         q.blk_start = di.blk_start; q.terms = di.terms;
@@ -220,23 +191,16 @@ int gfpl_gba_debug_system(gfpl_gba* l, int i, int iteration, double* U, double* 
     if (l->poisoned || (size_t)i >= l->last.size()) return GFPL_E_STATE;
     const GbaProb& q = l->last[(size_t)i];
     const GbaPlan& plan = l->plans[(size_t)i];
-    GBA_HIPCHK(hipSetDevice(gfpl_ctx_device(l->ctx)));
-    GBA_HIPCHK(hipStreamSynchronize(stream_of(l->ctx)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(l->ctx)));
+    GFPL_HIPCHK(hipStreamSynchronize(stream_of(l->ctx)));
     int32_t si[16];
-    GBA_HIPCHK(hipMemcpy(si, q.m.si, sizeof si, hipMemcpyDeviceToHost));
+    GFPL_HIPCHK(hipMemcpy(si, q.m.si, sizeof si, hipMemcpyDeviceToHost));
     if (si[GBA_SI_LAST_IT] != iteration) return GFPL_E_STATE;
-    const size_t nkf = (size_t)q.n.n.n_kf, npt = (size_t)q.n.n.n_pt, nls = (size_t)q.n.n.n_ls;
-    auto get = [](double* dst, const double* src, size_t cnt) {
-        if (!dst || cnt == 0) return hipSuccess;
-        return hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDeviceToHost);
-    };
-    GBA_HIPCHK(get(U, q.m.U, nkf * 36));
-    GBA_HIPCHK(get(g, q.m.gk, nkf * 6));
-    if (g) GBA_HIPCHK(get(g + nkf * 6, q.m.glm, 3 * npt + 6 * nls));
-    GBA_HIPCHK(get(V_pt, q.m.V, 9 * npt));
-    GBA_HIPCHK(get(V_ls, q.m.V + 9 * npt, 36 * nls));
-    GBA_HIPCHK(get(W_pt, q.m.W, 18 * (size_t)q.n.n_pt_pairs));
-    GBA_HIPCHK(get(W_ls, q.m.W + 18 * (size_t)q.n.n_pt_pairs, 36 * (size_t)q.n.n_ls_pairs));
+    const size_t npt = (size_t)q.n.n.n_pt, nls = (size_t)q.n.n.n_ls;
+    const int rc = ba_read_system(q.m, q.n.n, l->d_res + i, U, g, V_pt, V_ls, err);
+    if (rc != GFPL_OK) return rc;
+    GFPL_HIPCHK(get_doubles(W_pt, q.m.W, 18 * (size_t)q.n.n_pt_pairs));
+    GFPL_HIPCHK(get_doubles(W_ls, q.m.W + 18 * (size_t)q.n.n_pt_pairs, 36 * (size_t)q.n.n_ls_pairs));
     if (pairs) {
         size_t k = 0;
         for (size_t j = 0; j < npt + nls; ++j)
@@ -244,11 +208,6 @@ int gfpl_gba_debug_system(gfpl_gba* l, int i, int iteration, double* U, double* 
                 pairs[2 * k] = (int32_t)j;
                 pairs[2 * k + 1] = plan.pair_kf[(size_t)p];
             }
-    }
-    if (err) {
-        gfpl_lba_result r;
-        GBA_HIPCHK(hipMemcpy(&r, l->d_res + i, sizeof r, hipMemcpyDeviceToHost));
-        *err = r.err;
     }
     return GFPL_OK;
 }

@@ -259,6 +259,10 @@ struct BowFinishLds {
 constexpr int LBA_BLOCK = 256;    // threads of k_lba = observation rows per LDS chunk
 constexpr int LBA_ROW = 14;       // doubles per observation row: J_pose[6], J_landmark[6], |err|, w
 constexpr int LBA_MAX_KFS = 16;   // = GFPL_LBA_MAX_KFS (gfpl_lba.cpp asserts it)
+// slots of a Levenberg-Marquardt loop's state that the LBA (LbaLds::sd, ::si) and the GBA (GbaPtrs::sd, ::si)
+// share (gfpl_ba.hpp works on these); each solver's own words follow them
+enum { BA_SD_LAMBDA = 0, BA_SD_ERR, BA_SD_ERRPREV, BA_SD_ERRSUM, BA_SD_N2 };
+enum { BA_SI_ITERS = 0, BA_SI_STOP, BA_SI_STATUS, BA_SI_HMAX, BA_SI_DONE };
 struct LbaPtrs {
     double *X, *DX;               // [6 n_kf + 3 n_pt + 6 n_ls]
     double* rows;                 // [n_obs][LBA_ROW], points first
@@ -302,9 +306,9 @@ struct LbaLds {
     double* Tinv = c.take<double>(16 * kfs);
     double* rows = c.take<double>(LBA_BLOCK * LBA_ROW);
     double* red = c.take<double>(LBA_BLOCK);
-    double* sd = c.take<double>(8);      // lambda, err, err_prev, err sum, |DX|^2
+    double* sd = c.take<double>(8);      // BA_SD_*
     int* slot = c.take<int>(LBA_BLOCK);
-    int* si = c.take<int>(16);           // iters, stop, status, hmax, done, singular, accept
+    int* si = c.take<int>(16);           // BA_SI_*, then singular, accept
     int bytes = c.off;
     GFPL_HD LbaLds(unsigned char* smem, int kfs) : c(smem), kfs(kfs) {}
 };
@@ -431,10 +435,9 @@ constexpr int GBA_ROW = LBA_ROW;   // an observation row is the LBA's
 constexpr int GBA_LDLT_KFS = 6;    // block rows of the panel one workgroup of k_gba_ldlt factorises (below its copy of the diagonal block)
 constexpr int GBA_MAX_KFS = 256;   // = GFPL_GBA_MAX_KFS (gfpl_gba.cpp asserts it)
 constexpr int GBA_MAX_LDLT_ROWS = 24;   // the test override of GBA_LDLT_KFS: 36 (1 + rows) threads stay within 1024
-// slots of the loop state (GbaPtrs::sd, ::si)
-enum { GBA_SD_LAMBDA = 0, GBA_SD_ERR, GBA_SD_ERRPREV, GBA_SD_ERRSUM, GBA_SD_N2, GBA_SD_N2POSE };
-enum { GBA_SI_ITERS = 0, GBA_SI_STOP, GBA_SI_STATUS, GBA_SI_HMAX, GBA_SI_DONE, GBA_SI_DONE_NEXT, GBA_SI_SING, GBA_SI_UPDATE_IT,
-       GBA_SI_LAST_IT, GBA_SI_LDLT_BAD0, GBA_SI_LDLT_BAD1 };
+// slots of the loop state (GbaPtrs::sd, ::si): the BA_* prefix, then the GBA's own words
+enum { GBA_SD_N2POSE = BA_SD_N2 + 1 };
+enum { GBA_SI_DONE_NEXT = BA_SI_DONE + 1, GBA_SI_SING, GBA_SI_UPDATE_IT, GBA_SI_LAST_IT, GBA_SI_LDLT_BAD0, GBA_SI_LDLT_BAD1 };
 // the planner's index arrays of one problem, laid out alike in the pinned staging and on the device
 struct GbaIdx {
     Carver c;
@@ -463,8 +466,8 @@ struct GbaPtrs {
     double *W, *Y;                // [18 n_pt_pairs + 36 n_ls_pairs]
     double *q, *dmax;             // [n_lm] squared step, largest |diagonal| of each landmark
     double *S, *D, *gr;           // [6 n_kf][6 n_kf], [6 n_kf], [6 n_kf]: g_r, then the pose step
-    double* sd;                   // [8]  GBA_SD_*
-    int32_t* si;                  // [16] GBA_SI_*
+    double* sd;                   // [8]  BA_SD_*, GBA_SD_*
+    int32_t* si;                  // [16] BA_SI_*, GBA_SI_*
 };
 struct GbaMem {
     Carver c;

@@ -3,14 +3,7 @@
 // workspace of up to max_problems problems, the batched solve around k_lba.hip (one upload of the
 // problem records and index arrays, one launch, one copy of the results, one synchronisation) and
 // the test hook that reads a problem's last evaluated system back.
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
-#include "../../include/gfpl.h"
-#include "gfpl_kernels.hpp"
+#include "gfpl_host.hpp"
 
 using namespace gfpl;
 
@@ -31,17 +24,6 @@ struct gfpl_lba {
 
 namespace {
 
-#define LBA_HIPCHK(x)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (x);                                                            \
-        if (e_ != hipSuccess) {                                                         \
-            std::fprintf(stderr, "gfpl: %s failed: %s\n", #x, hipGetErrorString(e_));   \
-            return GFPL_E_HIP;                                                          \
-        }                                                                               \
-    } while (0)
-
-hipStream_t stream_of(const gfpl_ctx* c) { return (hipStream_t)gfpl_ctx_stream(c); }
-
 int check_counts(const gfpl_lba_counts& n) {
     if (n.n_kf < 1 || n.n_fix < 0 || n.n_pt < 0 || n.n_ls < 0 || n.n_pt_obs < 0 || n.n_ls_obs < 0) return GFPL_E_INVALID;
     if (n.n_kf > GFPL_LBA_MAX_KFS) return GFPL_E_CAPACITY;
@@ -59,8 +41,6 @@ int check_list(const int32_t* lm, const int32_t* kf, int n_obs, int n_lm, int n_
     }
     return GFPL_OK;
 }
-
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -98,7 +78,7 @@ int gfpl_lba_create(gfpl_ctx* c, const gfpl_lba_counts* caps, int max_problems, 
     const int rc = check_counts(*caps);
     if (rc != GFPL_OK) return rc;
     if (!gfpl_ctx_camera(c)) return GFPL_E_STATE;
-    LBA_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
     gfpl_lba* l = new gfpl_lba();
     l->ctx = c;
     l->caps = *caps;
@@ -148,9 +128,7 @@ int gfpl_lba_solve(gfpl_lba* l, const gfpl_lba_problem* problems, int n, const g
         const gfpl_lba_problem& p = problems[i];
         const int rc = gfpl_lba_check(&p);
         if (rc != GFPL_OK) return rc;
-        if (!p.x_kf || !p.T_kf || (p.n.n_fix > 0 && !p.T_fix)) return GFPL_E_INVALID;
-        if (p.n.n_pt > 0 && (!p.pt || !p.pt_obs || !p.pt_sigma)) return GFPL_E_INVALID;
-        if (p.n.n_ls > 0 && (!p.ls || !p.ls_obs || !p.ls_sigma)) return GFPL_E_INVALID;
+        if (!ba_problem_pointers_ok(p)) return GFPL_E_INVALID;
     }
     if (n > l->max_problems) return GFPL_E_CAPACITY;
     for (int i = 0; i < n; ++i) {
@@ -162,7 +140,7 @@ int gfpl_lba_solve(gfpl_lba* l, const gfpl_lba_problem* problems, int n, const g
     if (n == 0) return GFPL_OK;
     const gfpl_camera* cam = gfpl_ctx_camera(l->ctx);
     if (!cam) return GFPL_E_STATE;
-    LBA_HIPCHK(hipSetDevice(gfpl_ctx_device(l->ctx)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(l->ctx)));
     hipStream_t s = stream_of(l->ctx);
 
     // the records and the index arrays, staged once.  A problem's indices travel to its own workspace.
@@ -178,9 +156,7 @@ int gfpl_lba_solve(gfpl_lba* l, const gfpl_lba_problem* problems, int n, const g
         LbaProb& q = hp[i];
         std::memset(&q, 0, sizeof q);
         q.n = p.n;
-        q.x_kf = p.x_kf; q.T_kf = p.T_kf; q.T_fix = p.T_fix; q.pt = p.pt; q.ls = p.ls;
-        q.pt_obs = p.pt_obs; q.pt_sigma = p.pt_sigma; q.ls_obs = p.ls_obs; q.ls_sigma = p.ls_sigma;
-        q.x_out = p.x_out;
+        ba_fill_prob(q, p);
         q.lm_start = m.lm_start; q.obs_lm = m.obs_lm; q.obs_kf = m.obs_kf;
         q.m = m.p;
         l->last[(size_t)i] = q;
@@ -215,7 +191,7 @@ int gfpl_lba_solve(gfpl_lba* l, const gfpl_lba_problem* problems, int n, const g
     if (e == hipSuccess) {
         LbaArgs a;
         std::memset(&a, 0, sizeof a);
-        a.cam.fx = cam->fx; a.cam.fy = cam->fy; a.cam.cx = cam->cx; a.cam.cy = cam->cy; a.cam.b = cam->b;
+        a.cam = dev_cam(cam);
         a.homog_th = gfpl_ctx_config(l->ctx)->homog_th;
         a.prm = *prm;
         a.probs = l->d_probs;
@@ -237,38 +213,25 @@ int gfpl_lba_debug_system(gfpl_lba* l, int i, int iteration, double* U, double* 
     if (!l || i < 0 || iteration < 0) return GFPL_E_INVALID;
     if ((size_t)i >= l->last.size()) return GFPL_E_STATE;
     const LbaProb& q = l->last[(size_t)i];
-    LBA_HIPCHK(hipSetDevice(gfpl_ctx_device(l->ctx)));
-    LBA_HIPCHK(hipStreamSynchronize(stream_of(l->ctx)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(l->ctx)));
+    GFPL_HIPCHK(hipStreamSynchronize(stream_of(l->ctx)));
     int32_t state[8];
-    LBA_HIPCHK(hipMemcpy(state, q.m.state, sizeof state, hipMemcpyDeviceToHost));
+    GFPL_HIPCHK(hipMemcpy(state, q.m.state, sizeof state, hipMemcpyDeviceToHost));
     if (state[0] != iteration) return GFPL_E_STATE;
     const size_t nkf = (size_t)q.n.n_kf, npt = (size_t)q.n.n_pt, nls = (size_t)q.n.n_ls;
-    auto get = [](double* dst, const double* src, size_t cnt) {
-        if (!dst || cnt == 0) return hipSuccess;
-        return hipMemcpy(dst, src, cnt * sizeof(double), hipMemcpyDeviceToHost);
-    };
-    LBA_HIPCHK(get(U, q.m.U, nkf * 36));
-    LBA_HIPCHK(get(g, q.m.gk, nkf * 6));
-    if (g) LBA_HIPCHK(get(g + nkf * 6, q.m.glm, 3 * npt + 6 * nls));
-    LBA_HIPCHK(get(V_pt, q.m.V, 9 * npt));
-    LBA_HIPCHK(get(V_ls, q.m.V + 9 * npt, 36 * nls));
+    const int rc = ba_read_system(q.m, q.n, l->d_res + i, U, g, V_pt, V_ls, err);
+    if (rc != GFPL_OK) return rc;
     // the blocks of keyframes that do not observe a landmark are never written on the device: they are zero
     std::vector<int32_t> mask(npt + nls);
-    if (npt + nls) LBA_HIPCHK(hipMemcpy(mask.data(), q.m.mask, (npt + nls) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    LBA_HIPCHK(get(W_pt, q.m.W, nkf * 18 * npt));
-    LBA_HIPCHK(get(W_ls, q.m.W + nkf * 18 * npt, nkf * 36 * nls));
+    if (npt + nls) GFPL_HIPCHK(hipMemcpy(mask.data(), q.m.mask, (npt + nls) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GFPL_HIPCHK(get_doubles(W_pt, q.m.W, nkf * 18 * npt));
+    GFPL_HIPCHK(get_doubles(W_ls, q.m.W + nkf * 18 * npt, nkf * 36 * nls));
     for (size_t j = 0; j < npt + nls; ++j)
         for (size_t s = 0; s < nkf; ++s) {
             if ((mask[j] >> s) & 1) continue;
             if (j < npt) { if (W_pt) std::memset(W_pt + (j * nkf + s) * 18, 0, 18 * sizeof(double)); }
             else if (W_ls) std::memset(W_ls + ((j - npt) * nkf + s) * 36, 0, 36 * sizeof(double));
         }
-    if (err) {
-        // err of that iteration: the record's, which the loop leaves untouched after its last evaluation
-        gfpl_lba_result r;
-        LBA_HIPCHK(hipMemcpy(&r, l->d_res + i, sizeof r, hipMemcpyDeviceToHost));
-        *err = r.err;
-    }
     return GFPL_OK;
 }
 

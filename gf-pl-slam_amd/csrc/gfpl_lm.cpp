@@ -2,14 +2,7 @@
 // object that owns the store's device memory and the host mirror of the counts, apply (the planner,
 // one upload of the work items and ops, one launch per lane-group bucket that has work, one
 // synchronisation), fuse (the same with the planner of gfpl_lm_fuse_plan.cpp), gather and read.
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
-#include "../../include/gfpl.h"
-#include "gfpl_kernels.hpp"
+#include "gfpl_host.hpp"
 #include "gfpl_lm_fuse_plan.hpp"
 #include "gfpl_lm_plan.hpp"
 
@@ -36,17 +29,6 @@ struct gfpl_lmstore {
 
 namespace {
 
-#define LM_HIPCHK(x)                                                                    \
-    do {                                                                                \
-        hipError_t e_ = (x);                                                            \
-        if (e_ != hipSuccess) {                                                         \
-            std::fprintf(stderr, "gfpl: %s failed: %s\n", #x, hipGetErrorString(e_));   \
-            return GFPL_E_HIP;                                                          \
-        }                                                                               \
-    } while (0)
-
-hipStream_t stream_of(const gfpl_ctx* c) { return (hipStream_t)gfpl_ctx_stream(c); }
-
 LmStoreDev dev_of(const gfpl_lmstore* st) {
     const LmStoreMem m(st->base, st->lm_cap, st->obs_cap);
     return LmStoreDev{m.rows, m.count, m.med_idx, m.med, st->obs_cap};
@@ -58,7 +40,7 @@ extern "C" {
 
 int gfpl_lmstore_create(gfpl_ctx* c, int lm_cap, int obs_cap, int max_ops, gfpl_lmstore** out) {
     if (!c || !out || lm_cap < 1 || obs_cap < 1 || obs_cap > GFPL_LM_MAX_OBS || max_ops < 1) return GFPL_E_INVALID;
-    LM_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
     gfpl_lmstore* st = new gfpl_lmstore();
     st->ctx = c;
     st->lm_cap = lm_cap;
@@ -251,7 +233,7 @@ int gfpl_lmstore_gather(gfpl_lmstore* st, const int32_t* lm_ids, int n, uint8_t*
     if ((uintptr_t)desc_out & 15) return GFPL_E_INVALID;
     for (int i = 0; i < n; ++i)
         if (lm_ids[i] < 0 || lm_ids[i] >= st->lm_cap || st->counts[(size_t)lm_ids[i]] == 0) return GFPL_E_INVALID;
-    LM_HIPCHK(hipSetDevice(gfpl_ctx_device(st->ctx)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(st->ctx)));
     hipStream_t s = stream_of(st->ctx);
     if (n > st->ids_cap) {
         if (st->h_ids) (void)hipHostFree(st->h_ids);
@@ -287,7 +269,7 @@ int gfpl_lmstore_gather(gfpl_lmstore* st, const int32_t* lm_ids, int n, uint8_t*
 int gfpl_lmstore_read(gfpl_lmstore* st, int lm, int32_t* count, int32_t* med_idx, uint8_t* desc_list, uint8_t* med_desc) {
     if (!st || lm < 0 || lm >= st->lm_cap) return GFPL_E_INVALID;
     if (st->failed) return GFPL_E_STATE;
-    LM_HIPCHK(hipSetDevice(gfpl_ctx_device(st->ctx)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(st->ctx)));
     hipStream_t s = stream_of(st->ctx);
     const LmStoreDev sd = dev_of(st);
     hipError_t e = hipSuccess;
@@ -305,7 +287,7 @@ int gfpl_lmstore_read(gfpl_lmstore* st, int lm, int32_t* count, int32_t* med_idx
 int gfpl_lmstore_debug_ms(gfpl_lmstore* st, float* ms) {
     if (!st || !ms) return GFPL_E_INVALID;
     if (!st->timed) return GFPL_E_STATE;
-    LM_HIPCHK(hipEventElapsedTime(ms, st->ev0, st->ev1));
+    GFPL_HIPCHK(hipEventElapsedTime(ms, st->ev0, st->ev1));
     return GFPL_OK;
 }
 

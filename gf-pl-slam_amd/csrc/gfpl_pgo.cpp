@@ -2,14 +2,7 @@
 // workspace sizes, the object that owns the device workspace of up to max_problems problems, the
 // batched solve around k_pgo.hip (the planner's lists of every problem staged once and uploaded,
 // two launches, one copy of the results, one synchronisation) and the test hooks.
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
-#include "../../include/gfpl.h"
-#include "gfpl_kernels.hpp"
+#include "gfpl_host.hpp"
 #include "gfpl_pgo_plan.hpp"
 
 using namespace gfpl;
@@ -32,18 +25,6 @@ struct gfpl_pgo {
 
 namespace {
 
-#define PGO_HIPCHK(x)                                                                   \
-    do {                                                                                \
-        hipError_t e_ = (x);                                                            \
-        if (e_ != hipSuccess) {                                                         \
-            std::fprintf(stderr, "gfpl: %s failed: %s\n", #x, hipGetErrorString(e_));   \
-            return GFPL_E_HIP;                                                          \
-        }                                                                               \
-    } while (0)
-
-hipStream_t stream_of(const gfpl_ctx* c) { return (hipStream_t)gfpl_ctx_stream(c); }
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 int check_counts(const gfpl_pgo_counts& n) {
     if (n.n_kf < 1 || n.n_lc < 1 || n.n_edge < 1 || n.env_blocks < 0 || n.n_pt < 0 || n.n_ls < 0) return GFPL_E_INVALID;
     if ((int64_t)n.n_pt + n.n_ls > 0x3fffffff || n.env_blocks > 0x7fffffff / 64 || n.n_edge > 0x3fffffff) return GFPL_E_CAPACITY;
@@ -53,11 +34,6 @@ int check_counts(const gfpl_pgo_counts& n) {
 bool fits(const gfpl_pgo_counts& n, const gfpl_pgo_counts& caps) {
     return n.n_kf <= caps.n_kf && n.n_lc <= caps.n_lc && n.n_edge <= caps.n_edge && n.env_blocks <= caps.env_blocks &&
            n.n_pt <= caps.n_pt && n.n_ls <= caps.n_ls;
-}
-
-template <typename T>
-void put(T* dst, const std::vector<T>& src) {
-    if (!src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(T));
 }
 
 }  // namespace
@@ -80,7 +56,7 @@ int gfpl_pgo_create(gfpl_ctx* c, const gfpl_pgo_counts* caps, int max_problems, 
     if (!c || !caps || !out || max_problems < 1) return GFPL_E_INVALID;
     const int rc = check_counts(*caps);
     if (rc != GFPL_OK) return rc;
-    PGO_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(c)));
     gfpl_pgo* g = new gfpl_pgo();
     g->ctx = c;
     g->caps = *caps;
@@ -140,7 +116,7 @@ int gfpl_pgo_solve(gfpl_pgo* g, const gfpl_pgo_problem* problems, int n, const g
     for (int i = 0; i < n; ++i)
         if (!fits(plans[(size_t)i].n, g->caps)) return GFPL_E_CAPACITY;
     if (n == 0) return GFPL_OK;
-    PGO_HIPCHK(hipSetDevice(gfpl_ctx_device(g->ctx)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(g->ctx)));
     hipStream_t s = stream_of(g->ctx);
 
     PgoProb* hp = reinterpret_cast<PgoProb*>(g->stage + g->idx_stride * (size_t)g->max_problems);
@@ -209,8 +185,8 @@ int gfpl_pgo_debug_system(gfpl_pgo* g, int i, double* chi2, double* b, double* d
     if (!g || i < 0) return GFPL_E_INVALID;
     if (g->poisoned || (size_t)i >= g->last.size() || g->last_max_iters != 1) return GFPL_E_STATE;
     const PgoProb& q = g->last[(size_t)i];
-    PGO_HIPCHK(hipSetDevice(gfpl_ctx_device(g->ctx)));
-    PGO_HIPCHK(hipStreamSynchronize(stream_of(g->ctx)));
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(g->ctx)));
+    GFPL_HIPCHK(hipStreamSynchronize(stream_of(g->ctx)));
     auto get = [](void* dst, const void* src, size_t bytes) {
         if (!dst || bytes == 0) return hipSuccess;
         return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
@@ -218,25 +194,25 @@ int gfpl_pgo_debug_system(gfpl_pgo* g, int i, double* chi2, double* b, double* d
     const size_t nf = (size_t)q.n.n_free, nv = (size_t)q.n.n_vert, ne = (size_t)q.n.n_edge;
     if (chi2) {
         gfpl_pgo_result r;
-        PGO_HIPCHK(hipMemcpy(&r, g->d_res + i, sizeof r, hipMemcpyDeviceToHost));
+        GFPL_HIPCHK(hipMemcpy(&r, g->d_res + i, sizeof r, hipMemcpyDeviceToHost));
         *chi2 = r.chi2_0;
     }
-    PGO_HIPCHK(get(b, q.m.b, nf * 6 * sizeof(double)));
-    PGO_HIPCHK(get(diag, q.m.diag, nf * 36 * sizeof(double)));
-    if (nf > 0) PGO_HIPCHK(get(env, q.m.H, (size_t)q.n.env_blocks * 36 * sizeof(double)));
-    PGO_HIPCHK(get(env_first, q.env_first, nf * sizeof(int32_t)));
-    PGO_HIPCHK(get(vert, q.vert, nv * 4 * sizeof(int32_t)));
-    PGO_HIPCHK(get(edge, q.edge, ne * 4 * sizeof(int32_t)));
-    PGO_HIPCHK(get(Z, q.m.Z, ne * 16 * sizeof(double)));
-    PGO_HIPCHK(get(X0, q.m.X0, nv * 16 * sizeof(double)));
+    GFPL_HIPCHK(get(b, q.m.b, nf * 6 * sizeof(double)));
+    GFPL_HIPCHK(get(diag, q.m.diag, nf * 36 * sizeof(double)));
+    if (nf > 0) GFPL_HIPCHK(get(env, q.m.H, (size_t)q.n.env_blocks * 36 * sizeof(double)));
+    GFPL_HIPCHK(get(env_first, q.env_first, nf * sizeof(int32_t)));
+    GFPL_HIPCHK(get(vert, q.vert, nv * 4 * sizeof(int32_t)));
+    GFPL_HIPCHK(get(edge, q.edge, ne * 4 * sizeof(int32_t)));
+    GFPL_HIPCHK(get(Z, q.m.Z, ne * 16 * sizeof(double)));
+    GFPL_HIPCHK(get(X0, q.m.X0, nv * 16 * sizeof(double)));
     return GFPL_OK;
 }
 
 int gfpl_pgo_debug_ms(gfpl_pgo* g, float* ms_solve, float* ms_correct) {
     if (!g) return GFPL_E_INVALID;
     if (g->poisoned || !g->timed) return GFPL_E_STATE;
-    if (ms_solve) PGO_HIPCHK(hipEventElapsedTime(ms_solve, g->ev[0], g->ev[1]));
-    if (ms_correct) PGO_HIPCHK(hipEventElapsedTime(ms_correct, g->ev[1], g->ev[2]));
+    if (ms_solve) GFPL_HIPCHK(hipEventElapsedTime(ms_solve, g->ev[0], g->ev[1]));
+    if (ms_correct) GFPL_HIPCHK(hipEventElapsedTime(ms_correct, g->ev[1], g->ev[2]));
     return GFPL_OK;
 }
 

@@ -6,7 +6,7 @@
 // kernel reads the problem's loop state first and returns when the problem has ended (or, for the
 // phases of the solve, when this iteration's system is singular).  Per iteration `it` (0: the pre-pass):
 //   k_gba_poses    (it > 0) inverse poses of X, a lane per keyframe
-//   k_gba_rows     a lane per observation: J_pose[6], J_landmark[6], |err|, w (k_lba's rows)
+//   k_gba_rows     a lane per observation: J_pose[6], J_landmark[6], |err|, w (gfpl_ba.hpp's rows)
 //   k_gba_kf       a workgroup per keyframe: 42 lanes walk its observations IN LIST ORDER into U and g;
 //                  one more workgroup adds err in list order
 //   k_gba_lm       a lane per landmark: V, g and its coupling blocks W, ONE PER PAIR (landmark, keyframe)
@@ -23,82 +23,21 @@
 //   k_gba_update   X: poses through expmap / inverse / logmap, landmarks by addition
 // and k_gba_final writes T_kf, pt, ls and the record back.  No floating-point atomics; every sum's
 // order is a function of the problem alone, never of the grid (GbaGrid), the batch or timing.
-// The rules that differ from the LBA are GbaRules (gfpl_kernels.hpp), read where marked "RULE".
-#include "gfpl_kernels.hpp"
+// The rules that differ from the LBA are GbaRules (gfpl_kernels.hpp), read where marked "RULE".  The row
+// arithmetic (ledger GB8), the loop state's start, the pose update and the record are gfpl_ba.hpp's, one
+// text for both solvers.
+#include "gfpl_ba.hpp"
 
 namespace gfpl {
 
 namespace {
 
-#define GBA_ENDED(si) (((si)[GBA_SI_DONE] | (si)[GBA_SI_DONE_NEXT]) != 0)
+#define GBA_ENDED(si) (((si)[BA_SI_DONE] | (si)[GBA_SI_DONE_NEXT]) != 0)
 // this iteration's system is singular: a landmark block (k_gba_inv) or a pivot of S (k_gba_ldlt, whose
 // block columns alternate between two words so that no launch reads a word one of its workgroups writes)
 #define GBA_SINGULAR(si) (((si)[GBA_SI_SING] | (si)[GBA_SI_LDLT_BAD0] | (si)[GBA_SI_LDLT_BAD0 + 1]) != 0)
 
-// ---- the row arithmetic of k_lba.hip (:1997-2022 / :2110-2161 have the LBA's forms, ledger GB8),
-// restated here so that k_lba's code object stays byte for byte what it was
-GFPL_DEV void gba_jac(const DevCam& cam, double th, const double* g, double ex, double ey, double* J) {
-    const double gx = g[0], gy = g[1], gz = g[2];
-    const double gz2 = 1.0 / ref_max(th, gz * gz);
-    const double a = cam.fx * ex, b = cam.fy * ey;
-    J[0] = (gz2 * a) * gz;
-    J[1] = (gz2 * b) * gz;
-    J[2] = (-gz2) * (a * gx + b * gy);
-    J[3] = (-gz2) * (((a * gx) * gy + (b * gy) * gy) + (b * gz) * gz);
-    J[4] = gz2 * (((a * gx) * gx + (a * gz) * gz) + (b * gx) * gy);
-    J[5] = gz2 * ((b * gx) * gz - (a * gy) * gz);
-}
-
-GFPL_DEV double gba_jtr(const double* J, const double* Ti, int j) {
-    return (J[0] * Ti[0 * 4 + j] + J[1] * Ti[1 * 4 + j]) + J[2] * Ti[2 * 4 + j];
-}
-
-GFPL_DEV void gba_point_row(const DevCam& cam, double th, const double* Ti, const double* Xw, const double* obs, double s2,
-                            double* row) {
-    double Xc[3], uv[2], J[6];
-    se3_apply(Ti, Xw, Xc);
-    projection(cam, Xc, uv);
-    const double dx = obs[0] - uv[0], dy = obs[1] - uv[1];
-    const double nrm = sqrt(dx * dx + dy * dy);
-    gba_jac(cam, th, Xc, dx, dy, J);
-    const double d = ref_max(th, nrm);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) row[i] = J[i] / d;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        row[6 + j] = gba_jtr(J, Ti, j) / d;
-        row[9 + j] = 0.0;
-    }
-    row[12] = nrm;
-    row[13] = 1.0 / (1.0 + (nrm * nrm) * s2);
-}
-
-GFPL_DEV void gba_line_row(const DevCam& cam, double th, const double* Ti, const double* PQ, const double* l, double s2,
-                           double* row) {
-    double Pc[3], Qc[3], pu[2], qu[2], JP[6], JQ[6];
-    se3_apply(Ti, PQ, Pc);
-    se3_apply(Ti, PQ + 3, Qc);
-    projection(cam, Pc, pu);
-    projection(cam, Qc, qu);
-    const double e0 = (l[0] * pu[0] + l[1] * pu[1]) + l[2];
-    const double e1 = (l[0] * qu[0] + l[1] * qu[1]) + l[2];
-    const double nrm = sqrt(e0 * e0 + e1 * e1);
-    gba_jac(cam, th, Pc, e0, e1, JP);
-    gba_jac(cam, th, Qc, e0, e1, JQ);
-    const double d = ref_max(th, nrm);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) row[i] = (JP[i] * e0 + JQ[i] * e1) / d;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        row[6 + j] = (gba_jtr(JP, Ti, j) * e0) / d;
-        row[9 + j] = (gba_jtr(JQ, Ti, j) * e1) / d;
-    }
-    row[12] = nrm;
-    row[13] = 1.0 / (1.0 + (nrm * nrm) * s2);
-}
-
-GFPL_DEV bool gba_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and inf
-
+// (not shared with the LBA, which inverts the block explicitly)
 // LDL^T of a landmark's damped D x D block (its lower triangle) without pivoting, the big factorisation's
 // per-entry order: Fm holds L under the diagonal and the pivots on it.  False when a pivot is not
 // positive and finite.  (Not inverse3 / inverse6 as in k_lba: with every step applied a run reaches
@@ -115,7 +54,7 @@ GFPL_DEV bool gba_block_ldlt(const double* A, double* Fm) {
 #pragma unroll
             for (int m = 0; m < k; ++m) v = v - (Fm[i * D + m] * Fm[k * D + m]) * Fm[m * D + m];
             if (i == k) {
-                ok = ok && v > 0.0 && gba_finite(v);
+                ok = ok && v > 0.0 && ref_finite(v);
                 Fm[k * D + k] = v;
             } else {
                 Fm[i * D + k] = v / Fm[k * D + k];
@@ -219,7 +158,7 @@ GFPL_DEV bool gba_landmark_invert(const GbaProb& pr, int j, double lambda) {
 #pragma unroll
     for (int p = 0; p < D; ++p) {
         V[p * D + p] = V[p * D + p] + lambda * V[p * D + p];
-        ok = ok && V[p * D + p] > 0.0 && gba_finite(V[p * D + p]);
+        ok = ok && V[p * D + p] > 0.0 && ref_finite(V[p * D + p]);
     }
     ok = gba_block_ldlt<D>(V, Vi) && ok;
 #pragma unroll
@@ -287,12 +226,9 @@ __global__ void __launch_bounds__(GBA_BLOCK) k_gba_init(GbaArgs a) {
     if (i == 0) {
         double* sd = pr.m.sd;
         int32_t* si = pr.m.si;
-        sd[GBA_SD_LAMBDA] = a.prm.lambda_lm;
-        sd[GBA_SD_ERR] = 0.0;
-        sd[GBA_SD_ERRPREV] = 999999999.9;
-        sd[GBA_SD_ERRSUM] = 0.0; sd[GBA_SD_N2] = 0.0; sd[GBA_SD_N2POSE] = 0.0;
-        si[GBA_SI_ITERS] = 1; si[GBA_SI_STOP] = 0; si[GBA_SI_STATUS] = 0; si[GBA_SI_HMAX] = 0;
-        si[GBA_SI_DONE] = 0; si[GBA_SI_DONE_NEXT] = 0; si[GBA_SI_SING] = 0; si[GBA_SI_UPDATE_IT] = -1; si[GBA_SI_LAST_IT] = 0;
+        ba_state_init(sd, si, a.prm.lambda_lm);
+        sd[BA_SD_ERRSUM] = 0.0; sd[BA_SD_N2] = 0.0; sd[GBA_SD_N2POSE] = 0.0;
+        si[GBA_SI_DONE_NEXT] = 0; si[GBA_SI_SING] = 0; si[GBA_SI_UPDATE_IT] = -1; si[GBA_SI_LAST_IT] = 0;
         si[GBA_SI_LDLT_BAD0] = 0; si[GBA_SI_LDLT_BAD0 + 1] = 0;
     }
 }
@@ -335,7 +271,7 @@ __global__ void __launch_bounds__(GBA_BLOCK) k_gba_rows(GbaArgs a, int it) {
         const double* Xw = it > 0 ? pr.m.X + n6 + 3 * (size_t)j : pr.pt + 3 * (size_t)j;
         double P[3] = {Xw[0], Xw[1], Xw[2]};
         double ob[2] = {pr.pt_obs[2 * (size_t)o], pr.pt_obs[2 * (size_t)o + 1]};
-        gba_point_row(a.cam, a.homog_th, Ti, P, ob, pr.pt_sigma[o], row);
+        ba_point_row(a.cam, a.homog_th, Ti, P, ob, pr.pt_sigma[o], row);
     } else {
         const size_t ol = (size_t)(o - npo);
         const double* Lw = pr.ls + 6 * (size_t)(j - npt);   // line3D of the map, never X (:2366)
@@ -344,7 +280,7 @@ __global__ void __launch_bounds__(GBA_BLOCK) k_gba_rows(GbaArgs a, int it) {
         for (int i = 0; i < 6; ++i) PQ[i] = Lw[i];
         // RULE line_th_homog (:2386): the GBA's iterations keep Config::homogTh()
         const double th = (it > 0 && !a.rules.line_th_homog) ? 0.0000001 : a.homog_th;
-        gba_line_row(a.cam, th, Ti, PQ, l, pr.ls_sigma[ol], row);
+        ba_line_row(a.cam, th, Ti, PQ, l, pr.ls_sigma[ol], row);
     }
     double* gr = pr.m.rows + (size_t)o * GBA_ROW;
 #pragma unroll
@@ -386,7 +322,7 @@ __global__ void __launch_bounds__(GBA_BLOCK) k_gba_kf(GbaArgs a) {
         }
         __syncthreads();
     }
-    if (tid == 0) pr.m.sd[GBA_SD_ERRSUM] = sum;
+    if (tid == 0) pr.m.sd[BA_SD_ERRSUM] = sum;
 }
 
 __global__ void __launch_bounds__(GBA_BLOCK) k_gba_lm(GbaArgs a, int it) {
@@ -431,24 +367,24 @@ __global__ void __launch_bounds__(GBA_BLOCK) k_gba_control(GbaArgs a, int it) {
     si[GBA_SI_LDLT_BAD0 + 1] = 0;
     if (it == 0) {
         // `double err` starts undefined (:1964): pinned to 0.0; err /= (Npt_obs + Nls_obs), both 0 for good (:2204)
-        sd[GBA_SD_ERR] = sd[GBA_SD_ERRSUM] / 0.0;
+        sd[BA_SD_ERR] = sd[BA_SD_ERRSUM] / 0.0;
         const double hm = red[0];
         if (hm >= 2147483648.0) {
-            si[GBA_SI_STATUS] |= GFPL_GBA_HMAX_RANGE;
-            si[GBA_SI_HMAX] = 0x7fffffff;
-            si[GBA_SI_DONE] = 1;
+            si[BA_SI_STATUS] |= GFPL_GBA_HMAX_RANGE;
+            si[BA_SI_HMAX] = 0x7fffffff;
+            si[BA_SI_DONE] = 1;
         } else {
             const int h = (int)hm;
-            si[GBA_SI_HMAX] = h;
-            sd[GBA_SD_LAMBDA] = sd[GBA_SD_LAMBDA] * (double)h;
+            si[BA_SI_HMAX] = h;
+            sd[BA_SD_LAMBDA] = sd[BA_SD_LAMBDA] * (double)h;
         }
     } else {
         // RULE divisor_zero (:2479): Npt_obs + Nls_obs again; the LBA divides by Npt + Nls
-        const double err = sd[GBA_SD_ERRSUM] / (a.rules.divisor_zero ? 0.0 : (double)(npt + nls));
-        sd[GBA_SD_ERR] = err;
-        if (fabs(err - sd[GBA_SD_ERRPREV]) < eps) { si[GBA_SI_STOP] = GFPL_GBA_STOP_DERR; si[GBA_SI_DONE] = 1; }
-        else if (err < eps) { si[GBA_SI_STOP] = GFPL_GBA_STOP_ERR; si[GBA_SI_DONE] = 1; }
-        si[GBA_SI_ITERS] = it;
+        const double err = sd[BA_SD_ERRSUM] / (a.rules.divisor_zero ? 0.0 : (double)(npt + nls));
+        sd[BA_SD_ERR] = err;
+        if (fabs(err - sd[BA_SD_ERRPREV]) < eps) { si[BA_SI_STOP] = GFPL_GBA_STOP_DERR; si[BA_SI_DONE] = 1; }
+        else if (err < eps) { si[BA_SI_STOP] = GFPL_GBA_STOP_ERR; si[BA_SI_DONE] = 1; }
+        si[BA_SI_ITERS] = it;
     }
 }
 
@@ -457,7 +393,7 @@ __global__ void __launch_bounds__(GBA_BLOCK) k_gba_inv(GbaArgs a) {
     if (GBA_ENDED(pr.m.si)) return;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= pr.n.n.n_pt + pr.n.n.n_ls) return;
-    const double lambda = pr.m.sd[GBA_SD_LAMBDA];
+    const double lambda = pr.m.sd[BA_SD_LAMBDA];
     const bool ok = j < pr.n.n.n_pt ? gba_landmark_invert<3>(pr, j, lambda) : gba_landmark_invert<6>(pr, j, lambda);
     if (!ok) atomicOr(&pr.m.si[GBA_SI_SING], 1);
 }
@@ -480,7 +416,7 @@ __global__ void __launch_bounds__(64) k_gba_s(GbaArgs a) {
     if (rhs) val = pr.m.gk[6 * (size_t)ka + ri];
     else if (ka == kb) {
         const double u = pr.m.U[(size_t)ka * 36 + ri * 6 + ci];
-        val = ri == ci ? u + pr.m.sd[GBA_SD_LAMBDA] * u : u;
+        val = ri == ci ? u + pr.m.sd[BA_SD_LAMBDA] * u : u;
     } else val = 0.0;
     for (int t = pr.blk_start[blk]; t < pr.blk_start[blk + 1]; ++t) {
         const int j = pr.terms[3 * (size_t)t], pa = pr.terms[3 * (size_t)t + 1], pb = pr.terms[3 * (size_t)t + 2];
@@ -496,6 +432,7 @@ __global__ void __launch_bounds__(64) k_gba_s(GbaArgs a) {
     else pr.m.S[(6 * (size_t)ka + ri) * n6 + 6 * (size_t)kb + ci] = val;
 }
 
+// (S in HBM and a launch per block column; the LBA's S lives in LDS: not shared)
 // block column kb of the LDL^T of S's lower triangle without pivoting: the panel's L in place, the diagonal
 // block's L transposed above the diagonal (the block itself stays readable for the whole launch), the pivots in D.  v(i,k) = S(i,k) - sum_{m<k} (L_im L_km) D_m, one term at a time with m ascending:
 // a lane per entry takes the terms of the finished columns m < 6 kb, then one lane per row takes the
@@ -547,7 +484,7 @@ __global__ void __launch_bounds__(36 * (1 + GBA_MAX_LDLT_ROWS)) k_gba_ldlt(GbaAr
                 double v = L.part[r * 6 + cc];
                 for (int m = 0; m < cc; ++m) v = v - (L.Ld[r * 6 + m] * L.Ld[cc * 6 + m]) * L.Dd[m];
                 if (r == cc) {
-                    const bool good = gba_finite(v) && (a.rules.any_sign_pivot ? v != 0.0 : v > 0.0);
+                    const bool good = ref_finite(v) && (a.rules.any_sign_pivot ? v != 0.0 : v > 0.0);
                     if (!good) { bad = true; break; }
                     if (v < 0.0) L.flag[1] = 1;
                     L.Dd[cc] = v;
@@ -560,7 +497,7 @@ __global__ void __launch_bounds__(36 * (1 + GBA_MAX_LDLT_ROWS)) k_gba_ldlt(GbaAr
     }
     __syncthreads();
     if (blockIdx.x == 0 && tid == 0) {
-        if (L.flag[1]) si[GBA_SI_STATUS] |= GFPL_GBA_INDEFINITE;
+        if (L.flag[1]) si[BA_SI_STATUS] |= GFPL_GBA_INDEFINITE;
         si[mine] = L.flag[0];
     }
     if (L.flag[0]) return;
@@ -656,23 +593,23 @@ __global__ void __launch_bounds__(GBA_BLOCK) k_gba_step(GbaArgs a, int it) {
         }
     }
     if (tid != 0) return;
-    const double lambda = sd[GBA_SD_LAMBDA];
+    const double lambda = sd[BA_SD_LAMBDA];
     int accept = 1;
     if (it > 0) {
         // err > err_prev is never true under divisor_zero (err is +inf or NaN): every step is applied
-        if (sd[GBA_SD_ERR] > sd[GBA_SD_ERRPREV]) { sd[GBA_SD_LAMBDA] = lambda / a.prm.lambda_k; accept = 0; }
-        else sd[GBA_SD_LAMBDA] = lambda * a.prm.lambda_k;
+        if (sd[BA_SD_ERR] > sd[BA_SD_ERRPREV]) { sd[BA_SD_LAMBDA] = lambda / a.prm.lambda_k; accept = 0; }
+        else sd[BA_SD_LAMBDA] = lambda * a.prm.lambda_k;
     }
-    if (sing) { accept = 0; si[GBA_SI_STATUS] |= GFPL_GBA_SINGULAR; }
+    if (sing) { accept = 0; si[BA_SI_STATUS] |= GFPL_GBA_SINGULAR; }
     if (accept) si[GBA_SI_UPDATE_IT] = it;
-    sd[GBA_SD_N2] = n2;
+    sd[BA_SD_N2] = n2;
     if (it > 0 && sqrt(n2) < eps) {
-        si[GBA_SI_STOP] = GFPL_GBA_STOP_STEP;
-        si[GBA_SI_ITERS] = it;
+        si[BA_SI_STOP] = GFPL_GBA_STOP_STEP;
+        si[BA_SI_ITERS] = it;
         si[GBA_SI_DONE_NEXT] = 1;
     } else {
-        sd[GBA_SD_ERRPREV] = sd[GBA_SD_ERR];
-        si[GBA_SI_ITERS] = it + 1;
+        sd[BA_SD_ERRPREV] = sd[BA_SD_ERR];
+        si[BA_SI_ITERS] = it + 1;
         if (it + 1 >= a.prm.max_iters) si[GBA_SI_DONE_NEXT] = 1;
     }
 }
@@ -686,16 +623,7 @@ __global__ void __launch_bounds__(GBA_BLOCK) k_gba_update(GbaArgs a, int it) {
     const size_t n6 = 6 * (size_t)nkf, N = n6 + 3 * (size_t)pr.n.n.n_pt + 6 * (size_t)pr.n.n.n_ls;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     double* X = pr.m.X;
-    if (i < (size_t)nkf) {
-        double Tp[16], E[16], Ei[16], Tc[16], x[6];
-        expmap_se3(X + 6 * i, Tp);
-        expmap_se3(pr.m.DX + 6 * i, E);
-        inverse_se3(E, Ei);
-        mat4_mul(Tp, Ei, Tc);
-        logmap_se3(Tc, x);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) X[6 * i + k] = x[k];
-    }
+    if (i < (size_t)nkf) ba_pose_update(X + 6 * i, pr.m.DX + 6 * i);
     if (n6 + i < N) X[n6 + i] = X[n6 + i] + pr.m.DX[n6 + i];
 }
 
@@ -707,7 +635,7 @@ __global__ void __launch_bounds__(GBA_BLOCK) k_gba_final(GbaArgs a) {
     const size_t n6 = 6 * (size_t)nkf, np3 = 3 * (size_t)pr.n.n.n_pt, N = n6 + np3 + 6 * (size_t)pr.n.n.n_ls;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const double* X = pr.m.X;
-    if (!(si[GBA_SI_STATUS] & GFPL_GBA_HMAX_RANGE)) {
+    if (!(si[BA_SI_STATUS] & GFPL_GBA_HMAX_RANGE)) {
         if (i < (size_t)nkf) {
             double T[16];
             expmap_se3(X + 6 * i, T);
@@ -720,12 +648,7 @@ __global__ void __launch_bounds__(GBA_BLOCK) k_gba_final(GbaArgs a) {
         if (i >= n6 && i < n6 + np3) pr.pt[i - n6] = X[i];
         else if (i >= n6 + np3 && i < N) pr.ls[i - n6 - np3] = X[i];
     }
-    if (i == 0) {
-        gfpl_lba_result r;
-        r.iters = si[GBA_SI_ITERS]; r.stop = si[GBA_SI_STOP]; r.status = si[GBA_SI_STATUS]; r.hmax = si[GBA_SI_HMAX];
-        r.lambda = pr.m.sd[GBA_SD_LAMBDA]; r.err = pr.m.sd[GBA_SD_ERR]; r.err_prev = pr.m.sd[GBA_SD_ERRPREV];
-        *a.out = r;
-    }
+    if (i == 0) *a.out = ba_record(pr.m.sd, si);
 }
 
 int gba_max_lds_bytes(int n_kf) {

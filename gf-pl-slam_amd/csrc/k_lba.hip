@@ -17,82 +17,16 @@
 //          (h) X is updated (poses through expmap / inverse / logmap, landmarks by addition).
 //          Every sum's order is a function of the problem alone: no floating-point atomics.
 //          DESIGN.md §4h, ledger BA1-BA14.
-#include "gfpl_kernels.hpp"
+#include "gfpl_ba.hpp"
 
 namespace gfpl {
 
 namespace {
 
 constexpr int LBA_NACC = (LBA_MAX_KFS * 42 + 1 + LBA_BLOCK - 1) / LBA_BLOCK;   // reduction entries per lane
-enum { SD_LAMBDA = 0, SD_ERR, SD_ERRPREV, SD_ERRSUM, SD_N2 };
-enum { SI_ITERS = 0, SI_STOP, SI_STATUS, SI_HMAX, SI_DONE, SI_SING, SI_ACCEPT };
+enum { SI_SING = BA_SI_DONE + 1, SI_ACCEPT };   // the LBA's words after the BA_SI_* prefix
 
-// the six pose terms of :1277-1282 (the landmark's three are its first three) for the error (ex, ey)
-GFPL_DEV void lba_jac(const DevCam& cam, double th, const double* g, double ex, double ey, double* J) {
-    const double gx = g[0], gy = g[1], gz = g[2];
-    const double gz2 = 1.0 / ref_max(th, gz * gz);
-    const double a = cam.fx * ex, b = cam.fy * ey;
-    J[0] = (gz2 * a) * gz;
-    J[1] = (gz2 * b) * gz;
-    J[2] = (-gz2) * (a * gx + b * gy);
-    J[3] = (-gz2) * (((a * gx) * gy + (b * gy) * gy) + (b * gz) * gz);
-    J[4] = gz2 * (((a * gx) * gx + (a * gz) * gz) + (b * gx) * gy);
-    J[5] = gz2 * ((b * gx) * gz - (a * gy) * gz);
-}
-
-// J^T R, column j (Jij.transpose() * Tiw.block(0,0,3,3))
-GFPL_DEV double lba_jtr(const double* J, const double* Ti, int j) {
-    return (J[0] * Ti[0 * 4 + j] + J[1] * Ti[1 * 4 + j]) + J[2] * Ti[2 * 4 + j];
-}
-
-// point observation (:1252-1293): Ti is the inverse pose
-GFPL_DEV void lba_point_row(const DevCam& cam, double th, const double* Ti, const double* Xw, const double* obs, double s2,
-                            double* row) {
-    double Xc[3], uv[2], J[6];
-    se3_apply(Ti, Xw, Xc);
-    projection(cam, Xc, uv);
-    const double dx = obs[0] - uv[0], dy = obs[1] - uv[1];
-    const double nrm = sqrt(dx * dx + dy * dy);
-    lba_jac(cam, th, Xc, dx, dy, J);
-    const double d = ref_max(th, nrm);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) row[i] = J[i] / d;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        row[6 + j] = lba_jtr(J, Ti, j) / d;
-        row[9 + j] = 0.0;
-    }
-    row[12] = nrm;
-    row[13] = 1.0 / (1.0 + (nrm * nrm) * s2);
-}
-
-// line observation (:1331-1402); the iterations pass th = 1e-7 (:1575-1618)
-GFPL_DEV void lba_line_row(const DevCam& cam, double th, const double* Ti, const double* PQ, const double* l, double s2,
-                           double* row) {
-    double Pc[3], Qc[3], pu[2], qu[2], JP[6], JQ[6];
-    se3_apply(Ti, PQ, Pc);
-    se3_apply(Ti, PQ + 3, Qc);
-    projection(cam, Pc, pu);
-    projection(cam, Qc, qu);
-    const double e0 = (l[0] * pu[0] + l[1] * pu[1]) + l[2];
-    const double e1 = (l[0] * qu[0] + l[1] * qu[1]) + l[2];
-    const double nrm = sqrt(e0 * e0 + e1 * e1);
-    lba_jac(cam, th, Pc, e0, e1, JP);
-    lba_jac(cam, th, Qc, e0, e1, JQ);
-    const double d = ref_max(th, nrm);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) row[i] = (JP[i] * e0 + JQ[i] * e1) / d;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        row[6 + j] = (lba_jtr(JP, Ti, j) * e0) / d;
-        row[9 + j] = (lba_jtr(JQ, Ti, j) * e1) / d;
-    }
-    row[12] = nrm;
-    row[13] = 1.0 / (1.0 + (nrm * nrm) * s2);
-}
-
-GFPL_DEV bool lba_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and inf
-
+// the landmark blocks are inverted explicitly here (the GBA factorises them, ledger GB11): not shared
 template <int D>
 GFPL_DEV void lba_invert(const double* A, double* Ai);
 template <>
@@ -165,12 +99,12 @@ GFPL_DEV bool lba_landmark_invert(const LbaProb& pr, int j, double lambda, size_
 #pragma unroll
     for (int p = 0; p < D; ++p) {
         V[p * D + p] = V[p * D + p] + lambda * V[p * D + p];
-        ok = ok && V[p * D + p] > 0.0 && lba_finite(V[p * D + p]);
+        ok = ok && V[p * D + p] > 0.0 && ref_finite(V[p * D + p]);
     }
     lba_invert<D>(V, Vi);
 #pragma unroll
     for (int i = 0; i < D * D; ++i) {
-        ok = ok && lba_finite(Vi[i]);
+        ok = ok && ref_finite(Vi[i]);
         pr.m.Vi[voff + i] = Vi[i];
     }
 #pragma unroll
@@ -253,10 +187,7 @@ __global__ void __launch_bounds__(BLOCK) k_lba(LbaArgs a) {
         X[i] = v;
     }
     if (tid == 0) {
-        L.sd[SD_LAMBDA] = a.prm.lambda_lm;
-        L.sd[SD_ERR] = 0.0;
-        L.sd[SD_ERRPREV] = 999999999.9;
-        L.si[SI_ITERS] = 1; L.si[SI_STOP] = 0; L.si[SI_STATUS] = 0; L.si[SI_HMAX] = 0; L.si[SI_DONE] = 0;
+        ba_state_init(L.sd, L.si, a.prm.lambda_lm);
         pr.m.state[0] = 0;
     }
     __syncthreads();
@@ -298,14 +229,14 @@ __global__ void __launch_bounds__(BLOCK) k_lba(LbaArgs a) {
                     const double* Xw = it > 0 ? X + n6 + 3 * (size_t)j : pr.pt + 3 * (size_t)j;
                     double P[3] = {Xw[0], Xw[1], Xw[2]};
                     double ob[2] = {pr.pt_obs[2 * (size_t)o], pr.pt_obs[2 * (size_t)o + 1]};
-                    lba_point_row(a.cam, a.homog_th, Ti, P, ob, pr.pt_sigma[o], row);
+                    ba_point_row(a.cam, a.homog_th, Ti, P, ob, pr.pt_sigma[o], row);
                 } else {
                     const size_t ol = (size_t)(o - npo);
                     const double* Lw = pr.ls + 6 * (size_t)(j - npt);
                     double PQ[6], l[3] = {pr.ls_obs[3 * ol], pr.ls_obs[3 * ol + 1], pr.ls_obs[3 * ol + 2]};
 #pragma unroll
                     for (int i = 0; i < 6; ++i) PQ[i] = Lw[i];
-                    lba_line_row(a.cam, it > 0 ? 0.0000001 : a.homog_th, Ti, PQ, l, pr.ls_sigma[ol], row);
+                    ba_line_row(a.cam, it > 0 ? 0.0000001 : a.homog_th, Ti, PQ, l, pr.ls_sigma[ol], row);
                 }
                 double* gr = pr.m.rows + (size_t)o * LBA_ROW;
 #pragma unroll
@@ -346,7 +277,7 @@ __global__ void __launch_bounds__(BLOCK) k_lba(LbaArgs a) {
                 if (e < 36) pr.m.U[kf * 36 + e] = acc[u];
                 else pr.m.gk[kf * 6 + (e - 36)] = acc[u];
             } else if (t == nred - 1) {
-                L.sd[SD_ERRSUM] = acc[u];
+                L.sd[BA_SD_ERRSUM] = acc[u];
             }
         }
         __syncthreads();   // the rows (global) are visible to the block
@@ -369,7 +300,7 @@ __global__ void __launch_bounds__(BLOCK) k_lba(LbaArgs a) {
         if (tid == 0) {
             pr.m.state[0] = it;
             if (it == 0) {
-                L.sd[SD_ERR] = L.sd[SD_ERRSUM] / 0.0;   // err /= (Npt_obs + Nls_obs), both 0 for good
+                L.sd[BA_SD_ERR] = L.sd[BA_SD_ERRSUM] / 0.0;   // err /= (Npt_obs + Nls_obs), both 0 for good
                 double hm = 0.0;
                 for (int i = 0; i < BLOCK; ++i)
                     if (L.red[i] > hm) hm = L.red[i];
@@ -378,25 +309,25 @@ __global__ void __launch_bounds__(BLOCK) k_lba(LbaArgs a) {
                     if (d > hm) hm = d;
                 }
                 if (hm >= 2147483648.0) {
-                    L.si[SI_STATUS] |= GFPL_LBA_HMAX_RANGE;
-                    L.si[SI_HMAX] = 0x7fffffff;
-                    L.si[SI_DONE] = 1;
+                    L.si[BA_SI_STATUS] |= GFPL_LBA_HMAX_RANGE;
+                    L.si[BA_SI_HMAX] = 0x7fffffff;
+                    L.si[BA_SI_DONE] = 1;
                 } else {
                     const int h = (int)hm;
-                    L.si[SI_HMAX] = h;
-                    L.sd[SD_LAMBDA] = L.sd[SD_LAMBDA] * (double)h;
+                    L.si[BA_SI_HMAX] = h;
+                    L.sd[BA_SD_LAMBDA] = L.sd[BA_SD_LAMBDA] * (double)h;
                 }
             } else {
-                const double err = L.sd[SD_ERRSUM] / (double)(npt + nls);
-                L.sd[SD_ERR] = err;
-                if (fabs(err - L.sd[SD_ERRPREV]) < eps) { L.si[SI_STOP] = GFPL_LBA_STOP_DERR; L.si[SI_DONE] = 1; }
-                else if (err < eps) { L.si[SI_STOP] = GFPL_LBA_STOP_ERR; L.si[SI_DONE] = 1; }
-                L.si[SI_ITERS] = it;
+                const double err = L.sd[BA_SD_ERRSUM] / (double)(npt + nls);
+                L.sd[BA_SD_ERR] = err;
+                if (fabs(err - L.sd[BA_SD_ERRPREV]) < eps) { L.si[BA_SI_STOP] = GFPL_LBA_STOP_DERR; L.si[BA_SI_DONE] = 1; }
+                else if (err < eps) { L.si[BA_SI_STOP] = GFPL_LBA_STOP_ERR; L.si[BA_SI_DONE] = 1; }
+                L.si[BA_SI_ITERS] = it;
             }
         }
         __syncthreads();
-        if (L.si[SI_DONE]) break;
-        const double lambda = L.sd[SD_LAMBDA];
+        if (L.si[BA_SI_DONE]) break;
+        const double lambda = L.sd[BA_SD_LAMBDA];
 
         // (d) damped landmark blocks inverted
         {
@@ -410,7 +341,8 @@ __global__ void __launch_bounds__(BLOCK) k_lba(LbaArgs a) {
         }
         __syncthreads();
 
-        // (e) S (lower triangle) and its right-hand side, landmarks ascending, keyframes by the mask
+        // (e) S (lower triangle) and its right-hand side, landmarks ascending, keyframes by the mask; S, its
+        // factorisation and the solve stay in LDS (the GBA's take a launch per block column): not shared
         // (an entry belongs to one lane throughout; the masks pass through LDS a chunk at a time)
         if (!L.si[SI_SING]) {
             const int ne = n6 * (n6 + 1);
@@ -468,7 +400,7 @@ __global__ void __launch_bounds__(BLOCK) k_lba(LbaArgs a) {
                 }
                 __syncthreads();
                 const double dk = L.S[k * n6 + k];
-                if (!(dk > 0.0 && lba_finite(dk))) {
+                if (!(dk > 0.0 && ref_finite(dk))) {
                     if (tid == 0) L.si[SI_SING] = 1;
                     break;   // uniform: every lane reads the same pivot
                 }
@@ -524,48 +456,39 @@ __global__ void __launch_bounds__(BLOCK) k_lba(LbaArgs a) {
 
         // the lambda rule (:1662-1678); a singular solve is DX = 0 with the update skipped
         if (tid == 0) {
-            L.sd[SD_N2] = n2;
+            L.sd[BA_SD_N2] = n2;
             int accept = 1;
             if (it > 0) {
-                if (L.sd[SD_ERR] > L.sd[SD_ERRPREV]) { L.sd[SD_LAMBDA] = lambda / a.prm.lambda_k; accept = 0; }
-                else L.sd[SD_LAMBDA] = lambda * a.prm.lambda_k;
+                if (L.sd[BA_SD_ERR] > L.sd[BA_SD_ERRPREV]) { L.sd[BA_SD_LAMBDA] = lambda / a.prm.lambda_k; accept = 0; }
+                else L.sd[BA_SD_LAMBDA] = lambda * a.prm.lambda_k;
             }
-            if (sing) { accept = 0; L.si[SI_STATUS] |= GFPL_LBA_SINGULAR; }
+            if (sing) { accept = 0; L.si[BA_SI_STATUS] |= GFPL_LBA_SINGULAR; }
             L.si[SI_ACCEPT] = accept;
         }
         __syncthreads();
 
         // (h) the update (:1443-1451, :1669-1677): X_i = logmap(expmap(X_i) inverse(expmap(DX_i)))
         if (L.si[SI_ACCEPT]) {
-            if (tid < nkf) {
-                double Tp[16], E[16], Ei[16], Tc[16], x[6];
-                expmap_se3(X + 6 * tid, Tp);
-                expmap_se3(L.dx + 6 * tid, E);
-                inverse_se3(E, Ei);
-                mat4_mul(Tp, Ei, Tc);
-                logmap_se3(Tc, x);
-#pragma unroll
-                for (int i = 0; i < 6; ++i) X[6 * tid + i] = x[i];
-            }
+            if (tid < nkf) ba_pose_update(X + 6 * tid, L.dx + 6 * tid);
             for (size_t i = (size_t)n6 + tid; i < N; i += BLOCK) X[i] = X[i] + pr.m.DX[i];
         }
         if (tid == 0) {
-            if (it > 0 && sqrt(L.sd[SD_N2]) < eps) {
-                L.si[SI_STOP] = GFPL_LBA_STOP_STEP;
-                L.si[SI_ITERS] = it;
-                L.si[SI_DONE] = 1;
+            if (it > 0 && sqrt(L.sd[BA_SD_N2]) < eps) {
+                L.si[BA_SI_STOP] = GFPL_LBA_STOP_STEP;
+                L.si[BA_SI_ITERS] = it;
+                L.si[BA_SI_DONE] = 1;
             } else {
-                L.sd[SD_ERRPREV] = L.sd[SD_ERR];
-                L.si[SI_ITERS] = it + 1;
-                if (it + 1 >= a.prm.max_iters) L.si[SI_DONE] = 1;
+                L.sd[BA_SD_ERRPREV] = L.sd[BA_SD_ERR];
+                L.si[BA_SI_ITERS] = it + 1;
+                if (it + 1 >= a.prm.max_iters) L.si[BA_SI_DONE] = 1;
             }
         }
         __syncthreads();
-        if (L.si[SI_DONE]) break;
+        if (L.si[BA_SI_DONE]) break;
     }
 
     // write back (:1691-1712) unless Hmax left the reference's defined behaviour
-    if (!(L.si[SI_STATUS] & GFPL_LBA_HMAX_RANGE)) {
+    if (!(L.si[BA_SI_STATUS] & GFPL_LBA_HMAX_RANGE)) {
         if (tid < nkf) {
             double T[16];
             expmap_se3(X + 6 * tid, T);
@@ -578,12 +501,7 @@ __global__ void __launch_bounds__(BLOCK) k_lba(LbaArgs a) {
         for (size_t i = tid; i < 3 * (size_t)npt; i += BLOCK) pr.pt[i] = X[n6 + i];
         for (size_t i = tid; i < 6 * (size_t)nls; i += BLOCK) pr.ls[i] = X[(size_t)n6 + 3 * (size_t)npt + i];
     }
-    if (tid == 0) {
-        gfpl_lba_result r;
-        r.iters = L.si[SI_ITERS]; r.stop = L.si[SI_STOP]; r.status = L.si[SI_STATUS]; r.hmax = L.si[SI_HMAX];
-        r.lambda = L.sd[SD_LAMBDA]; r.err = L.sd[SD_ERR]; r.err_prev = L.sd[SD_ERRPREV];
-        a.out[blockIdx.x] = r;
-    }
+    if (tid == 0) a.out[blockIdx.x] = ba_record(L.sd, L.si);
 }
 
 hipError_t launch_lba(const LbaArgs& a, int n, hipStream_t s) {

@@ -24,8 +24,6 @@ namespace {
 enum { PD_LAMBDA = 0, PD_NU, PD_CHI2, PD_CHI2T, PD_DMAX, PD_SCALE, PD_CHI2_0, PD_CHI2_PREV };
 enum { PI_ITERS = 0, PI_STOP, PI_STATUS, PI_REJECTS, PI_DONE, PI_SING, PI_ACCEPT, PI_REJ_IT };
 
-GFPL_DEV bool pgo_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN and inf
-
 // the unit quaternion (x, y, z, w), w >= 0, of the rotation of D by the four-branch rule
 GFPL_DEV void pgo_quat(const double* D, double* q) {
     const double r00 = D[0], r01 = D[1], r02 = D[2], r10 = D[4], r11 = D[5], r12 = D[6], r20 = D[8], r21 = D[9], r22 = D[10];
@@ -308,7 +306,7 @@ __global__ void __launch_bounds__(PGO_BLOCK) k_pgo(PgoArgs a) {
                 }
                 __syncthreads();
                 const double dk = *pgo_at(pr, pr.m.L, k, k);
-                if (!(dk > 0.0 && pgo_finite(dk))) { sing = true; break; }   // uniform: every lane reads the same pivot
+                if (!(dk > 0.0 && ref_finite(dk))) { sing = true; break; }   // uniform: every lane reads the same pivot
                 if (tid == 0) pr.m.D[k] = dk;
                 for (int i = k + 1 + tid; i < imax; i += PGO_BLOCK) {
                     if (pr.env_first[i / 6] > kb) continue;
@@ -386,7 +384,7 @@ __global__ void __launch_bounds__(PGO_BLOCK) k_pgo(PgoArgs a) {
                 const double chi2 = L.sd[PD_CHI2], chi2t = L.sd[PD_CHI2T], sc = L.sd[PD_SCALE];
                 bool accept = false;
                 double rho = 0.0;
-                if (!sing && pgo_finite(chi2t) && sc > 0.0 && pgo_finite(sc)) {
+                if (!sing && ref_finite(chi2t) && sc > 0.0 && ref_finite(sc)) {
                     rho = (chi2 - chi2t) / sc;
                     // a trial the sum cannot tell from the current poses is taken too; the chi2 rule then stops
                     accept = rho > 0.0 || chi2t - chi2 <= (64.0 * eps) * chi2;

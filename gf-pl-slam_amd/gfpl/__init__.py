@@ -1286,13 +1286,16 @@ class Context:
         check(self.L.gfpl_bow_score(self.h, va, vb, n, _ptr(out)), "bow_score")
         return out.cpu().numpy()[:n].copy()
 
-    def _lba_run(self, problems, prm, debug=None):
-        caps = [max([getattr(p.counts, f) for p in problems] + [1 if f == "n_kf" else 0]) for f, _ in LbaCounts._fields_]
+    def _ba_run(self, solver_cls, problems, prm, debug=None):
+        """One solve of a solver made for these problems (LbaSolver or GbaSolver) and closed after it."""
+        counts = []
         for p in problems:   # the host rules first: nothing is allocated for a refused problem
-            rc = p.check()
+            rc, c = solver_cls.check_counts(p)
             if rc != 0:
-                raise GfplError(rc, "lba_check")
-        solver = LbaSolver(self, caps, max(len(problems), 1))
+                raise GfplError(rc, solver_cls._name + "_check")
+            counts.append(c)
+        caps = [max(col) for col in zip(solver_cls._min_caps, *counts)]
+        solver = solver_cls(self, caps, max(len(problems), 1))
         try:
             return solver.solve(problems, prm, debug)
         finally:
@@ -1304,7 +1307,7 @@ class Context:
         a dict: result (LbaResult), T_kf [n_kf][4][4] = expmap_se3(X), pt, ls and x_kf, the pose part of
         X at exit.  The problems' own arrays are not changed."""
         single = isinstance(problems, LbaProblem)
-        res = self._lba_run([problems] if single else list(problems), params if params is not None else LbaParams.default())
+        res = self._ba_run(LbaSolver, [problems] if single else list(problems), params if params is not None else LbaParams.default())
         return res[0] if single else res
 
     def lbaDebugSystem(self, problem: LbaProblem, iteration: int, params: Optional[LbaParams] = None):
@@ -1313,21 +1316,7 @@ class Context:
         rows, pose columns), g and err — from a solve of iteration + 1 iterations."""
         prm = LbaParams.default() if params is None else LbaParams.from_buffer_copy(params)
         prm.max_iters = iteration + 1
-        return self._lba_run([problem], prm, debug=(0, iteration))[1]
-
-    def _gba_run(self, problems, prm, debug=None):
-        counts = []
-        for p in problems:   # the host rules first: nothing is allocated for a refused problem
-            rc, c = gbaCheck(p)
-            if rc != 0:
-                raise GfplError(rc, "gba_check")
-            counts.append(c.flat())
-        caps = [max(col) for col in zip(*counts)] if counts else [1, 0, 0, 0, 0, 0, 0, 0, 0]
-        solver = GbaSolver(self, caps, max(len(problems), 1))
-        try:
-            return solver.solve(problems, prm, debug)
-        finally:
-            solver.close()
+        return self._ba_run(LbaSolver, [problem], prm, debug=(0, iteration))[1]
 
     def globalBundleAdjustment(self, problems, params: Optional[LbaParams] = None):
         """MapHandler::globalBundleAdjustment's solver (levMarquardtOptimizationGBA, src/mapHandler.cpp:
@@ -1335,7 +1324,7 @@ class Context:
         keyframe 0, which is a fixed pose.  Per problem the dict of Context.localBundleAdjustment.  The
         problems' own arrays are not changed."""
         single = isinstance(problems, LbaProblem)
-        res = self._gba_run([problems] if single else list(problems), params if params is not None else LbaParams.default())
+        res = self._ba_run(GbaSolver, [problems] if single else list(problems), params if params is not None else LbaParams.default())
         return res[0] if single else res
 
     def gbaDebugSystem(self, problem: LbaProblem, iteration: int, params: Optional[LbaParams] = None):
@@ -1344,7 +1333,7 @@ class Context:
         diagonal per (landmark, keyframe) pair: W_pt [point pairs][3][6], W_ls [line pairs][6][6], pairs."""
         prm = LbaParams.default() if params is None else LbaParams.from_buffer_copy(params)
         prm.max_iters = iteration + 1
-        return self._gba_run([problem], prm, debug=(0, iteration))[1]
+        return self._ba_run(GbaSolver, [problem], prm, debug=(0, iteration))[1]
 
     def _pgo_run(self, problems, prm, debug=None):
         counts = []
@@ -1428,79 +1417,25 @@ class Event:
             pass
 
 
-class GbaSolver:
-    """gfpl_gba: the device workspace of up to max_problems global bundle adjustments whose counts
-    (GbaCounts, or the nine numbers of GbaCounts.of) stay within caps; solve() may be called any number
-    of times.  The context cannot be closed while the solver is open."""
+class _BaSolver:
+    """What LbaSolver and GbaSolver share: the object behind gfpl_<_name>_create / _solve / _debug_system /
+    _destroy.  A subclass names the entry points, makes its counts type from caps and says what the
+    debug hook returns besides U, g, V_pt and V_ls."""
+    _name = ""
+    _min_caps = ()      # the counts of a solver made for no problem
 
     def __init__(self, ctx: "Context", caps, max_problems: int):
         self.ctx, self.L = ctx, ctx.L
-        self.caps = caps if isinstance(caps, GbaCounts) else GbaCounts.of(*[int(v) for v in caps])
+        self.caps = self._counts(caps)
         self.h = C.c_void_p()
-        check(self.L.gfpl_gba_create(ctx.h, C.byref(self.caps), max_problems, C.byref(self.h)), "gba_create")
+        check(self._c("create")(ctx.h, C.byref(self.caps), max_problems, C.byref(self.h)), self._name + "_create")
 
-    def solve(self, problems, params: Optional[LbaParams] = None, debug=None):
-        """Per problem a dict (see Context.globalBundleAdjustment).  debug = (i, iteration): also the
-        system of gfpl_gba_debug_system for problem i, as the second element of a pair."""
-        import torch
-        prm = params if params is not None else LbaParams.default()
-        n = len(problems)
-        dev = torch.device("cuda", self.ctx.device)
-        devs, structs = [], (LbaProblemStruct * max(n, 1))()
-        for i, p in enumerate(problems):
-            d = {k: torch.from_numpy(p.a[k].copy()).to(dev) for k, _ in LBA_DOUBLES}
-            d["x_out"] = d["x_kf"].clone()   # (a problem whose Hmax leaves the int range writes nothing)
-            devs.append(d)
-            structs[i] = p.struct(d)
-        out = (LbaResult * max(n, 1))()
-        torch.cuda.synchronize()
-        check(self.L.gfpl_gba_solve(self.h, structs, n, C.byref(prm), out), "gba_solve")
-        res = []
-        for i, d in enumerate(devs):
-            res.append(dict(result=LbaResult.from_buffer_copy(out[i]), T_kf=d["T_kf"].cpu().numpy().reshape(-1, 4, 4),
-                            pt=d["pt"].cpu().numpy(), ls=d["ls"].cpu().numpy(), x_kf=d["x_out"].cpu().numpy()))
-        if debug is None:
-            return res
-        i, it = debug
-        rc, g = gbaCheck(problems[i])
-        check(rc, "gba_check")
-        c = g.n
-        sysd = dict(U=np.zeros((c.n_kf, 6, 6)), g=np.zeros(6 * c.n_kf + 3 * c.n_pt + 6 * c.n_ls),
-                    V_pt=np.zeros((c.n_pt, 3, 3)), V_ls=np.zeros((c.n_ls, 6, 6)),
-                    W_pt=np.zeros((g.n_pt_pairs, 3, 6)), W_ls=np.zeros((g.n_ls_pairs, 6, 6)),
-                    pairs=np.zeros((g.n_pt_pairs + g.n_ls_pairs, 2), np.int32))
-        err = C.c_double(0.0)
-        check(self.L.gfpl_gba_debug_system(self.h, i, it, *[_ptr(sysd[k]) for k in ("U", "g", "V_pt", "V_ls", "W_pt", "W_ls", "pairs")],
-                                           C.byref(err)), "gba_debug_system")
-        sysd["err"] = np.float64(err.value)
-        return res, sysd
-
-    def close(self):
-        if getattr(self, "h", None):
-            check(self.L.gfpl_gba_destroy(self.h), "gba_destroy")
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class LbaSolver:
-    """gfpl_lba: the device workspace of up to max_problems local bundle adjustments whose counts stay
-    within caps (n_kf, n_fix, n_pt, n_ls, n_pt_obs, n_ls_obs); solve() may be called any number of
-    times.  The context cannot be closed while the solver is open."""
-
-    def __init__(self, ctx: "Context", caps, max_problems: int):
-        self.ctx, self.L = ctx, ctx.L
-        self.caps = caps if isinstance(caps, LbaCounts) else LbaCounts(*[int(v) for v in caps])
-        self.h = C.c_void_p()
-        check(self.L.gfpl_lba_create(ctx.h, C.byref(self.caps), max_problems, C.byref(self.h)), "lba_create")
+    def _c(self, what):
+        return getattr(self.L, "gfpl_%s_%s" % (self._name, what))
 
     def solve(self, problems, params: Optional[LbaParams] = None, debug=None):
         """Per problem a dict (see Context.localBundleAdjustment).  debug = (i, iteration): also the
-        system of gfpl_lba_debug_system for problem i, as the second element of a pair."""
+        system of the solver's debug hook for problem i, as the second element of a pair."""
         import torch
         prm = params if params is not None else LbaParams.default()
         n = len(problems)
@@ -1513,7 +1448,7 @@ class LbaSolver:
             structs[i] = p.struct(d)
         out = (LbaResult * max(n, 1))()
         torch.cuda.synchronize()
-        check(self.L.gfpl_lba_solve(self.h, structs, n, C.byref(prm), out), "lba_solve")
+        check(self._c("solve")(self.h, structs, n, C.byref(prm), out), self._name + "_solve")
         res = []
         for i, d in enumerate(devs):
             res.append(dict(result=LbaResult.from_buffer_copy(out[i]), T_kf=d["T_kf"].cpu().numpy().reshape(-1, 4, 4),
@@ -1523,17 +1458,16 @@ class LbaSolver:
         i, it = debug
         c = problems[i].counts
         sysd = dict(U=np.zeros((c.n_kf, 6, 6)), g=np.zeros(6 * c.n_kf + 3 * c.n_pt + 6 * c.n_ls),
-                    V_pt=np.zeros((c.n_pt, 3, 3)), V_ls=np.zeros((c.n_ls, 6, 6)),
-                    W_pt=np.zeros((c.n_pt, c.n_kf, 3, 6)), W_ls=np.zeros((c.n_ls, c.n_kf, 6, 6)))
-        err = C.c_double(0.0)
-        check(self.L.gfpl_lba_debug_system(self.h, i, it, *[_ptr(sysd[k]) for k in ("U", "g", "V_pt", "V_ls", "W_pt", "W_ls")],
-                                           C.byref(err)), "lba_debug_system")
+                    V_pt=np.zeros((c.n_pt, 3, 3)), V_ls=np.zeros((c.n_ls, 6, 6)), **self._debug_blocks(problems[i]))
+        err = C.c_double(0.0)   # (the dict's order is the hook's argument order)
+        check(self._c("debug_system")(self.h, i, it, *[_ptr(v) for v in sysd.values()], C.byref(err)),
+              self._name + "_debug_system")
         sysd["err"] = np.float64(err.value)
         return res, sysd
 
     def close(self):
         if getattr(self, "h", None):
-            check(self.L.gfpl_lba_destroy(self.h), "lba_destroy")
+            check(self._c("destroy")(self.h), self._name + "_destroy")
             self.h = None
 
     def __del__(self):
@@ -1541,6 +1475,50 @@ class LbaSolver:
             self.close()
         except Exception:
             pass
+
+
+class GbaSolver(_BaSolver):
+    """gfpl_gba: the device workspace of up to max_problems global bundle adjustments whose counts
+    (GbaCounts, or the nine numbers of GbaCounts.of) stay within caps; solve() may be called any number
+    of times (per problem the dict of Context.globalBundleAdjustment).  The context cannot be closed
+    while the solver is open."""
+    _name, _min_caps = "gba", (1, 0, 0, 0, 0, 0, 0, 0, 0)
+
+    @staticmethod
+    def _counts(caps):
+        return caps if isinstance(caps, GbaCounts) else GbaCounts.of(*[int(v) for v in caps])
+
+    @staticmethod
+    def check_counts(problem: LbaProblem):
+        rc, c = gbaCheck(problem)
+        return rc, c.flat()
+
+    @staticmethod
+    def _debug_blocks(problem: LbaProblem):
+        rc, g = gbaCheck(problem)
+        check(rc, "gba_check")
+        return dict(W_pt=np.zeros((g.n_pt_pairs, 3, 6)), W_ls=np.zeros((g.n_ls_pairs, 6, 6)),
+                    pairs=np.zeros((g.n_pt_pairs + g.n_ls_pairs, 2), np.int32))
+
+
+class LbaSolver(_BaSolver):
+    """gfpl_lba: the device workspace of up to max_problems local bundle adjustments whose counts stay
+    within caps (n_kf, n_fix, n_pt, n_ls, n_pt_obs, n_ls_obs); solve() may be called any number of
+    times.  The context cannot be closed while the solver is open."""
+    _name, _min_caps = "lba", (1, 0, 0, 0, 0, 0)
+
+    @staticmethod
+    def _counts(caps):
+        return caps if isinstance(caps, LbaCounts) else LbaCounts(*[int(v) for v in caps])
+
+    @staticmethod
+    def check_counts(problem: LbaProblem):
+        return problem.check(), [getattr(problem.counts, f) for f, _ in LbaCounts._fields_]
+
+    @staticmethod
+    def _debug_blocks(problem: LbaProblem):
+        c = problem.counts
+        return dict(W_pt=np.zeros((c.n_pt, c.n_kf, 3, 6)), W_ls=np.zeros((c.n_ls, c.n_kf, 6, 6)))
 
 
 # ------------------------------------------------- loop-closure pose graph --
