@@ -262,6 +262,48 @@ hipError_t launch_pgo(const PgoArgs& a, int n, hipStream_t s);
 // the map correction of n problems whose largest job count is max_jobs (> 0)
 hipError_t launch_pgo_correct(const PgoProb* probs, int n, int max_jobs, hipStream_t s);
 
+// the map's index half (k_kfmap.hip); all pointers device.  The arrays are KfMapMem's: KfMapLm one
+// kind's (points or lines), KfMapCore what the kinds share and the workspace.
+struct KfMapLm {
+    uint8_t *alive, *local, *inlier;
+    int32_t *nobs, *owner, *obs;  // obs [cap][obs_cap]
+    int32_t* idx;                 // [kf_cap][rows] the features' idx
+    int32_t* kf_n;                // [kf_cap] rows in use
+    int rows, cap;
+    int next;                     // the kind's next id when the call starts
+};
+struct KfMapCore {
+    int32_t* hdr;                 // KFMAP_H_*
+    uint8_t *kf_alive, *kf_local;
+    int32_t* graph;               // [kf_cap][kf_cap]
+    int32_t *tile, *seen0, *seen1, *pend, *first_row, *pair_n0, *pair_slot;
+    int kf_cap, obs_cap;
+    int n_kf;                     // keyframes when the call starts
+};
+// one observe call: kf0 >= 0 the keyframe-pair stage (pairs = kf0 row, kf1 row), kf0 < 0 the local-map
+// stage (pairs = row of sel_ids, row of unm_rows).  epoch: the object's call number (> 0)
+struct KfMapObserve {
+    int kind, kf0, kf1, n, n_sel, n_unm, epoch;
+    const int32_t *pairs, *sel_ids, *unm_rows;
+    int32_t* lm_out;
+};
+// one ordered compaction over n items into out, its count into hdr[slot]
+enum { KFMAP_SEL_LOCAL = 0, KFMAP_SEL_LOCAL_UNSEEN, KFMAP_SEL_ALIVE, KFMAP_SEL_UNMATCHED, KFMAP_SEL_BAD };
+struct KfMapSelect {
+    int mode, kf, n, slot;        // kf: kf1 of LOCAL_UNSEEN, the keyframe of UNMATCHED
+    int min_lm_obs, cull_age;     // BAD
+    int32_t* out;
+};
+hipError_t enqueue_kfmap_add_keyframe(const KfMapCore& c, const KfMapLm& pt, const KfMapLm& ls, int n_pt, int n_ls, hipStream_t s);
+hipError_t enqueue_kfmap_observe(const KfMapCore& c, const KfMapLm& L, const KfMapObserve& a, hipStream_t s);
+hipError_t enqueue_kfmap_form_local_map(const KfMapCore& c, const KfMapLm& pt, const KfMapLm& ls, int min_lm_cov_graph,
+                                        int min_kf_local_map, hipStream_t s);
+hipError_t enqueue_kfmap_select(const KfMapCore& c, const KfMapLm& L, const KfMapSelect& a, hipStream_t s);
+// the compaction of the landmarks to remove (a.mode = KFMAP_SEL_BAD), then their removal
+hipError_t enqueue_kfmap_remove_bad(const KfMapCore& c, const KfMapLm& L, const KfMapSelect& a, hipStream_t s);
+hipError_t enqueue_kfmap_set_inlier(const KfMapCore& c, const KfMapLm& L, const int32_t* ids, int n, int value, hipStream_t s);
+hipError_t enqueue_kfmap_erase_keyframe(const KfMapCore& c, int kf, hipStream_t s);
+
 }  // namespace gfpl
 
 namespace gfpl {

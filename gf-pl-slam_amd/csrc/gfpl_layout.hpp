@@ -507,4 +507,50 @@ struct GbaSubstLds {
 };
 static_assert(8 * 6 * GBA_MAX_KFS <= 64 * 1024, "GbaSubstLds at GBA_MAX_KFS fits the default dynamic LDS");
 
+// ---- the map's index half (gfpl_kfmap, k_kfmap.hip, gfpl_kfmap.cpp): per keyframe its flags, row
+// counts and the features' idx at a fixed stride; per landmark and kind its flags, kf_obs_list at a
+// fixed stride of obs_cap with its length, and the keyframe that owns it; full_graph at a stride of
+// kf_cap; then the calls' header and workspace.  Landmark arrays are [2] by kind (0 points, 1 lines).
+constexpr int KFMAP_TILE = 2048;     // = GFPL_KFMAP_TILE: items per workgroup of a compaction
+constexpr int KFMAP_BLOCK = 256;     // threads of every k_kfmap kernel; a thread takes TILE / BLOCK consecutive items
+constexpr int KFMAP_HDR = 16;        // int32 words of the header (KFMAP_H_*), copied to the host once per call
+// the first KFMAP_H_CALL words are a call's own (zeroed when it starts), the others the map's
+enum { KFMAP_H_ERR = 0, KFMAP_H_COUNT0, KFMAP_H_COUNT1, KFMAP_H_FIRST_NEW, KFMAP_H_CALL, KFMAP_H_NKF = KFMAP_H_CALL, KFMAP_H_NEXT_PT, KFMAP_H_NEXT_LS };
+constexpr int KFMAP_ERR_INVALID = 1, KFMAP_ERR_CAPACITY = 2;
+struct KfMapMem {
+    Carver c;
+    int kf_cap, rows[2], lm_cap[2], obs_cap;
+    size_t max_rows = (size_t)(rows[0] > rows[1] ? rows[0] : rows[1]);
+    size_t max_lm = (size_t)(lm_cap[0] > lm_cap[1] ? lm_cap[0] : lm_cap[1]);
+    size_t max_items = max_rows > max_lm ? max_rows : max_lm;
+    size_t n_tiles = (max_items + KFMAP_BLOCK - 1) / KFMAP_BLOCK;   // an observe call scans per workgroup of pairs
+    int32_t* hdr = c.take<int32_t>(KFMAP_HDR);
+    uint8_t* kf_alive = c.take<uint8_t>((size_t)kf_cap);
+    uint8_t* kf_local = c.take<uint8_t>((size_t)kf_cap);
+    int32_t* kf_n[2] = {c.take<int32_t>((size_t)kf_cap), c.take<int32_t>((size_t)kf_cap)};
+    int32_t* kf_idx[2] = {c.take<int32_t>((size_t)kf_cap * rows[0]), c.take<int32_t>((size_t)kf_cap * rows[1])};
+    int32_t* graph = c.take<int32_t>((size_t)kf_cap * kf_cap);
+    uint8_t* lm_alive[2] = {c.take<uint8_t>((size_t)lm_cap[0]), c.take<uint8_t>((size_t)lm_cap[1])};
+    uint8_t* lm_local[2] = {c.take<uint8_t>((size_t)lm_cap[0]), c.take<uint8_t>((size_t)lm_cap[1])};
+    uint8_t* lm_inlier[2] = {c.take<uint8_t>((size_t)lm_cap[0]), c.take<uint8_t>((size_t)lm_cap[1])};
+    int32_t* lm_nobs[2] = {c.take<int32_t>((size_t)lm_cap[0]), c.take<int32_t>((size_t)lm_cap[1])};
+    int32_t* lm_owner[2] = {c.take<int32_t>((size_t)lm_cap[0]), c.take<int32_t>((size_t)lm_cap[1])};
+    int32_t* lm_obs[2] = {c.take<int32_t>((size_t)lm_cap[0] * obs_cap), c.take<int32_t>((size_t)lm_cap[1] * obs_cap)};
+    // workspace.  tile: the compactions' tile sums, then their exclusive scan in place.  seen0 / seen1: the
+    // call number that last named a value in column 0 / 1 of a pairs array (0: never).  pend: appends a
+    // landmark receives within the running call (all 0 between calls).  first_row: remove_bad's lowest
+    // carrying row (all INT32_MAX between calls).  pair_n0 / pair_slot: per pair of an observe call, its
+    // landmark's list length before the call and the place of its own entry.
+    int32_t* tile = c.take<int32_t>(n_tiles + 1);
+    int32_t* seen0 = c.take<int32_t>(max_items);
+    int32_t* seen1 = c.take<int32_t>(max_rows);
+    int32_t* pend = c.take<int32_t>(max_lm);
+    int32_t* first_row = c.take<int32_t>(max_lm);
+    int32_t* pair_n0 = c.take<int32_t>(max_rows);
+    int32_t* pair_slot = c.take<int32_t>(max_rows);
+    size_t bytes = (c.off + 255) & ~(size_t)255;
+    KfMapMem(char* base, int kf_cap, int pt_rows, int ls_rows, int pt_lm_cap, int ls_lm_cap, int obs_cap)
+        : c{0, base}, kf_cap(kf_cap), rows{pt_rows, ls_rows}, lm_cap{pt_lm_cap, ls_lm_cap}, obs_cap(obs_cap) {}
+};
+
 }  // namespace gfpl

@@ -718,6 +718,27 @@ def hiplib() -> C.CDLL:
             "gfpl_lmstore_gather": ([P, P, C.c_int, P, P], C.c_int),
             "gfpl_lmstore_read": ([P, C.c_int, P, P, P, P], C.c_int),
             "gfpl_lmstore_debug_ms": ([P, P], C.c_int),
+            "gfpl_default_kfmap_params": ([P], None),
+            "gfpl_kfmap_bytes": ([P], C.c_int64),
+            "gfpl_kfmap_create": ([P, P, C.POINTER(P)], C.c_int),
+            "gfpl_kfmap_destroy": ([P], C.c_int),
+            "gfpl_kfmap_counts": ([P, P, P, P], C.c_int),
+            "gfpl_kfmap_add_keyframe": ([P, C.c_int, C.c_int, P], C.c_int),
+            "gfpl_kfmap_observe_pairs": ([P, C.c_int, C.c_int, C.c_int, P, C.c_int, P, P, P], C.c_int),
+            "gfpl_kfmap_observe_local": ([P, C.c_int, C.c_int, P, C.c_int, P, C.c_int, P, C.c_int, P], C.c_int),
+            "gfpl_kfmap_form_local_map": ([P, P], C.c_int),
+            "gfpl_kfmap_select": ([P, C.c_int, C.c_int, C.c_int, P, P], C.c_int),
+            "gfpl_kfmap_unmatched": ([P, C.c_int, C.c_int, P, P], C.c_int),
+            "gfpl_kfmap_local_keyframes": ([P, P, P], C.c_int),
+            "gfpl_kfmap_remove_bad": ([P, P, P, P, P, P], C.c_int),
+            "gfpl_kfmap_set_inlier": ([P, C.c_int, P, C.c_int, C.c_int], C.c_int),
+            "gfpl_kfmap_erase_keyframe": ([P, C.c_int], C.c_int),
+            "gfpl_kfmap_read_keyframe": ([P, C.c_int, P, P, P], C.c_int),
+            "gfpl_kfmap_write_keyframe_idx": ([P, C.c_int, C.c_int, C.c_int, C.c_int, P], C.c_int),
+            "gfpl_kfmap_read_landmarks": ([P, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P], C.c_int),
+            "gfpl_kfmap_write_landmarks": ([P, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P], C.c_int),
+            "gfpl_kfmap_export_graph": ([P, P, P, P, P, P, P, P, P], C.c_int),
+            "gfpl_kfmap_debug_ms": ([P, P], C.c_int),
             "gfpl_default_gba_params": ([P], None),
             "gfpl_gba_check": ([P, P], C.c_int),
             "gfpl_gba_workspace": ([P, P, P], C.c_int),
@@ -1844,6 +1865,228 @@ class LandmarkStore:
     def close(self):
         if getattr(self, "h", None):
             check(self.L.gfpl_lmstore_destroy(self.h), "lmstore_destroy")
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+KFMAP_TILE = 2048                                         # GFPL_KFMAP_TILE
+KFMAP_LOCAL, KFMAP_LOCAL_UNSEEN, KFMAP_ALIVE = 0, 1, 2    # GFPL_KFMAP_*
+KFMAP_POINTS, KFMAP_LINES = 0, 1
+
+
+class KfMapCaps(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("kf_cap", "pt_rows", "ls_rows", "pt_lm_cap", "ls_lm_cap", "obs_cap")]
+
+
+class KfMapParams(C.Structure):
+    """gfpl_kfmap_params: Config::minLMCovGraph, minKFLocalMap, minLMObs and removeBadMapLandmarks' literal 10."""
+    _fields_ = [(k, C.c_int32) for k in ("min_lm_cov_graph", "min_kf_local_map", "min_lm_obs", "cull_age")]
+
+    @classmethod
+    def default(cls, **over) -> "KfMapParams":
+        p = cls()
+        hiplib().gfpl_default_kfmap_params(C.byref(p))
+        for k, v in over.items():
+            setattr(p, k, v)
+        return p
+
+
+class KfMapKf(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("alive", "local", "n_pt", "n_ls")]
+
+
+def kfmap_bytes(caps: KfMapCaps) -> int:
+    """gfpl_kfmap_bytes (host only): device bytes of an object with these caps, -1 for caps it refuses."""
+    return int(hiplib().gfpl_kfmap_bytes(C.byref(caps)))
+
+
+class KeyframeMap:
+    """gfpl_kfmap: the index half of one map on the device (the features' idx of every keyframe,
+    kf_obs_list and owner of every landmark, full_graph, the local flags) with MapHandler's operations
+    on it.  Device lists go in and come out as torch int32 tensors; the *_rc methods return the C
+    code, the others raise GfplError.  The context cannot be closed while the map is open."""
+
+    def __init__(self, ctx: "Context", kf_cap: int, pt_rows: int, ls_rows: int, pt_lm_cap: int, ls_lm_cap: int, obs_cap: int):
+        self.ctx, self.L = ctx, ctx.L
+        self.caps = KfMapCaps(kf_cap, pt_rows, ls_rows, pt_lm_cap, ls_lm_cap, obs_cap)
+        self.h = C.c_void_p()
+        check(self.L.gfpl_kfmap_create(ctx.h, C.byref(self.caps), C.byref(self.h)), "kfmap_create")
+
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.ctx.device)
+
+    def _out(self, n: int):
+        import torch
+        t = torch.full((max(int(n), 1),), -7, dtype=torch.int32, device=self._dev())
+        torch.cuda.synchronize()
+        return t
+
+    def _in(self, a, cols: int = 0):
+        """a device int32 tensor of the list (tensors pass through), synchronised before the C call"""
+        import torch
+        if not isinstance(a, torch.Tensor):
+            a = np.ascontiguousarray(a, np.int32)
+            a = a.reshape(-1, cols) if cols else a.reshape(-1)
+            a = torch.from_numpy(a.copy()).to(self._dev())
+        torch.cuda.synchronize()
+        return a
+
+    def counts(self):
+        """(n_kf, next point id, next line id)"""
+        v = [C.c_int32(0) for _ in range(3)]
+        check(self.L.gfpl_kfmap_counts(self.h, *[C.byref(x) for x in v]), "kfmap_counts")
+        return tuple(x.value for x in v)
+
+    def add_keyframe_rc(self, n_pt: int, n_ls: int):
+        kf = C.c_int32(-1)
+        rc = self.L.gfpl_kfmap_add_keyframe(self.h, int(n_pt), int(n_ls), C.byref(kf))
+        return rc, kf.value
+
+    def add_keyframe(self, n_pt: int, n_ls: int) -> int:
+        rc, kf = self.add_keyframe_rc(n_pt, n_ls)
+        check(rc, "kfmap_add_keyframe")
+        return kf
+
+    def observe_pairs_rc(self, kind: int, kf0: int, kf1: int, pairs):
+        """(code, lm_out tensor [n], first_new, n_new)"""
+        p = self._in(pairs, 2)
+        n = int(p.shape[0])
+        out = self._out(n)
+        first, new = C.c_int32(-1), C.c_int32(-1)
+        rc = self.L.gfpl_kfmap_observe_pairs(self.h, int(kind), int(kf0), int(kf1), _ptr(p), n, _ptr(out),
+                                             C.byref(first), C.byref(new))
+        return rc, out[:n], first.value, new.value
+
+    def observe_pairs(self, kind: int, kf0: int, kf1: int, pairs):
+        rc, out, first, new = self.observe_pairs_rc(kind, kf0, kf1, pairs)
+        check(rc, "kfmap_observe_pairs")
+        return out, first, new
+
+    def observe_local_rc(self, kind: int, kf1: int, pairs, sel_ids, unm_rows):
+        """(code, lm_out tensor [n])"""
+        p, sel, unm = self._in(pairs, 2), self._in(sel_ids), self._in(unm_rows)
+        n = int(p.shape[0])
+        out = self._out(n)
+        rc = self.L.gfpl_kfmap_observe_local(self.h, int(kind), int(kf1), _ptr(p), n, _ptr(sel), int(sel.shape[0]),
+                                             _ptr(unm), int(unm.shape[0]), _ptr(out))
+        return rc, out[:n]
+
+    def observe_local(self, kind: int, kf1: int, pairs, sel_ids, unm_rows):
+        rc, out = self.observe_local_rc(kind, kf1, pairs, sel_ids, unm_rows)
+        check(rc, "kfmap_observe_local")
+        return out
+
+    def form_local_map(self, params: Optional[KfMapParams] = None) -> None:
+        prm = params if params is not None else KfMapParams.default()
+        check(self.L.gfpl_kfmap_form_local_map(self.h, C.byref(prm)), "kfmap_form_local_map")
+
+    def select(self, kind: int, which: int, kf1: int = 0):
+        """device tensor of the selected landmark ids, in map order"""
+        out = self._out(self.counts()[1 + int(kind)] if kind in (0, 1) else 0)
+        n = C.c_int32(-1)
+        check(self.L.gfpl_kfmap_select(self.h, int(kind), int(which), int(kf1), _ptr(out), C.byref(n)), "kfmap_select")
+        return out[: n.value]
+
+    def unmatched(self, kind: int, kf: int):
+        """device tensor of kf's rows without a landmark, in row order"""
+        out = self._out(self.caps.ls_rows if kind else self.caps.pt_rows)
+        n = C.c_int32(-1)
+        check(self.L.gfpl_kfmap_unmatched(self.h, int(kind), int(kf), _ptr(out), C.byref(n)), "kfmap_unmatched")
+        return out[: n.value]
+
+    def local_keyframes(self) -> np.ndarray:
+        out = np.zeros(self.caps.kf_cap, np.int32)
+        n = C.c_int32(-1)
+        check(self.L.gfpl_kfmap_local_keyframes(self.h, _ptr(out), C.byref(n)), "kfmap_local_keyframes")
+        return out[: n.value]
+
+    def remove_bad(self, params: Optional[KfMapParams] = None):
+        """(removed point ids, removed line ids): device tensors in map order"""
+        prm = params if params is not None else KfMapParams.default()
+        _, npt, nls = self.counts()
+        pt, ls = self._out(npt), self._out(nls)
+        a, b = C.c_int32(-1), C.c_int32(-1)
+        check(self.L.gfpl_kfmap_remove_bad(self.h, C.byref(prm), _ptr(pt), C.byref(a), _ptr(ls), C.byref(b)), "kfmap_remove_bad")
+        return pt[: a.value], ls[: b.value]
+
+    def set_inlier_rc(self, kind: int, ids, value: int) -> int:
+        t = self._in(ids)
+        return self.L.gfpl_kfmap_set_inlier(self.h, int(kind), _ptr(t), int(t.shape[0]), int(value))
+
+    def set_inlier(self, kind: int, ids, value: int) -> None:
+        check(self.set_inlier_rc(kind, ids, value), "kfmap_set_inlier")
+
+    def erase_keyframe_rc(self, kf: int) -> int:
+        return self.L.gfpl_kfmap_erase_keyframe(self.h, int(kf))
+
+    def erase_keyframe(self, kf: int) -> None:
+        check(self.erase_keyframe_rc(kf), "kfmap_erase_keyframe")
+
+    def read_keyframe(self, kf: int) -> dict:
+        """alive, local, and the features' idx of the rows in use"""
+        rec = KfMapKf()
+        pt, ls = np.zeros(self.caps.pt_rows, np.int32), np.zeros(self.caps.ls_rows, np.int32)
+        check(self.L.gfpl_kfmap_read_keyframe(self.h, int(kf), C.byref(rec), _ptr(pt), _ptr(ls)), "kfmap_read_keyframe")
+        return dict(alive=rec.alive, local=rec.local, pt_idx=pt[: rec.n_pt], ls_idx=ls[: rec.n_ls])
+
+    def write_keyframe_idx_rc(self, kind: int, kf: int, row0: int, idx) -> int:
+        a = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        return self.L.gfpl_kfmap_write_keyframe_idx(self.h, int(kind), int(kf), int(row0), len(a), _ptr(a))
+
+    def write_keyframe_idx(self, kind: int, kf: int, row0: int, idx) -> None:
+        check(self.write_keyframe_idx_rc(kind, kf, row0, idx), "kfmap_write_keyframe_idx")
+
+    def read_landmarks(self, kind: int, id0: int = 0, n: Optional[int] = None) -> dict:
+        """alive, local, inlier, n_obs, owner [n] and kf_obs [n][obs_cap] of ids [id0, id0 + n); n: up to the next id"""
+        n = self.counts()[1 + int(kind)] - id0 if n is None else int(n)
+        d = dict(alive=np.zeros(n, np.uint8), local=np.zeros(n, np.uint8), inlier=np.zeros(n, np.uint8),
+                 n_obs=np.zeros(n, np.int32), owner=np.zeros(n, np.int32), kf_obs=np.zeros((n, self.caps.obs_cap), np.int32))
+        check(self.L.gfpl_kfmap_read_landmarks(self.h, int(kind), int(id0), n, *[_ptr(d[k]) for k in
+              ("alive", "local", "inlier", "n_obs", "owner", "kf_obs")]), "kfmap_read_landmarks")
+        return d
+
+    def write_landmarks_rc(self, kind: int, id0: int, alive, local, inlier, n_obs, owner, kf_obs) -> int:
+        a = [np.ascontiguousarray(v, np.uint8).reshape(-1) for v in (alive, local, inlier)]
+        b = [np.ascontiguousarray(v, np.int32).reshape(-1) for v in (n_obs, owner)]
+        o = np.ascontiguousarray(kf_obs, np.int32).reshape(len(a[0]), self.caps.obs_cap)
+        return self.L.gfpl_kfmap_write_landmarks(self.h, int(kind), int(id0), len(a[0]), *[_ptr(v) for v in a + b + [o]])
+
+    def write_landmarks(self, kind: int, id0: int, alive, local, inlier, n_obs, owner, kf_obs) -> None:
+        check(self.write_landmarks_rc(kind, id0, alive, local, inlier, n_obs, owner, kf_obs), "kfmap_write_landmarks")
+
+    def export_graph(self) -> dict:
+        """alive, full_graph and the two ownership lists as gfpl_pgo_problem takes them (numpy)"""
+        nkf, npt, nls = self.counts()
+        d = dict(alive=np.zeros(nkf, np.uint8), full_graph=np.zeros((nkf, nkf), np.int32))
+        for k, n in (("pt", npt), ("ls", nls)):
+            d[k + "_kf_start"], d[k + "_kf_idx"] = np.zeros(nkf + 1, np.int32), np.zeros(max(n, 1), np.int32)
+            d[k + "_freed"] = np.zeros(max(n, 1), np.uint8)
+        check(self.L.gfpl_kfmap_export_graph(self.h, *[_ptr(d[k]) for k in (
+            "alive", "full_graph", "pt_kf_start", "pt_kf_idx", "pt_freed", "ls_kf_start", "ls_kf_idx", "ls_freed")]),
+            "kfmap_export_graph")
+        for k, n in (("pt", npt), ("ls", nls)):
+            d[k + "_kf_idx"] = d[k + "_kf_idx"][: d[k + "_kf_start"][nkf]]
+            d[k + "_freed"] = d[k + "_freed"][:n]
+        return d
+
+    def nbytes(self) -> int:
+        return kfmap_bytes(self.caps)
+
+    def last_device_ms(self) -> float:
+        """gfpl_kfmap_debug_ms: device time between the first and the last kernel of the last call"""
+        ms = C.c_float(0.0)
+        check(self.L.gfpl_kfmap_debug_ms(self.h, C.byref(ms)), "kfmap_debug_ms")
+        return float(ms.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            check(self.L.gfpl_kfmap_destroy(self.h), "kfmap_destroy")
             self.h = None
 
     def __del__(self):

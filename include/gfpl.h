@@ -844,6 +844,117 @@ int  gfpl_map_fuse_search(gfpl_ctx* ctx, const gfpl_fuse_map* m, const gfpl_fuse
  * gate launches of kind 0 (points) or 1 (lines); GFPL_E_STATE when that kind launched fewer than all three. */
 int  gfpl_map_fuse_debug_ms(gfpl_ctx* ctx, int kind, float* ms /*HOST [3]*/);
 
+/* ------------------------------------- the map's index half ------------- */
+/* The integer bookkeeping of MapHandler (src/mapHandler.cpp) as one device object per map (k_kfmap.hip,
+ * gfpl_kfmap.cpp, DESIGN.md §4m, ledger KM1-KM9): stereo_pt[i]->idx / stereo_ls[i]->idx of every
+ * keyframe, kf_obs_list of every landmark, full_graph, map_points_kf_idx / map_lines_kf_idx and the
+ * `local` flags, with the reference's operations on them.  kind 0 is points, 1 lines; the two id
+ * spaces are independent (max_pt_idx, max_ls_idx).  obs_list, dir_list, sigma_list, pts_list, the 3D
+ * geometry, med_obs_dir and the lc_status machine stay with the caller; the descriptors are
+ * gfpl_lmstore's.  map_*_kf_idx is kept as one `owner` per landmark: keyframe k's list is the
+ * landmarks it owns in ascending id (KM3).
+ * Every call synchronises once.  A refused call changes nothing.  GFPL_E_INVALID wins over
+ * GFPL_E_CAPACITY when a call's device data earns both.  After GFPL_E_HIP from a launch, copy or
+ * synchronisation the state is unknown: every call returns GFPL_E_STATE until the object is destroyed. */
+#define GFPL_KFMAP_TILE 2048          /* landmarks (or rows) per workgroup of the ordered compactions */
+#define GFPL_KFMAP_LOCAL        0     /* alive && local (localBundleAdjustment :1133-1166, gfpl_fuse_map) */
+#define GFPL_KFMAP_LOCAL_UNSEEN 1     /* alive && local && kf_obs_list.back() != kf1 (:520, :642) */
+#define GFPL_KFMAP_ALIVE        2     /* map_points[j] != NULL (globalBundleAdjustment) */
+typedef struct gfpl_kfmap gfpl_kfmap;
+typedef struct gfpl_kfmap_caps {
+    int32_t kf_cap;                   /* keyframes */
+    int32_t pt_rows, ls_rows;         /* features of one keyframe */
+    int32_t pt_lm_cap, ls_lm_cap;     /* landmark ids ever given out (freed ids are not reused) */
+    int32_t obs_cap;                  /* entries of one kf_obs_list, 2..GFPL_LM_MAX_OBS */
+} gfpl_kfmap_caps;
+typedef struct gfpl_kfmap_params { int32_t min_lm_cov_graph, min_kf_local_map, min_lm_obs, cull_age; } gfpl_kfmap_params;
+void gfpl_default_kfmap_params(gfpl_kfmap_params* prm);   /* 30, 3, 2, 10 (src/config.cpp:40, 51, 53; the literal of :2558) */
+typedef struct gfpl_kfmap_kf { int32_t alive, local, n_pt, n_ls; } gfpl_kfmap_kf;
+/* Host only: the device bytes of an object with these caps (state and workspace), -1 for caps it refuses. */
+int64_t gfpl_kfmap_bytes(const gfpl_kfmap_caps* caps);
+/* MapHandler::initialize's resets (:42-58): no keyframe, no landmark, both next ids 0, a zero graph.
+ * GFPL_E_INVALID for a NULL pointer, a cap < 1, kf_cap > 65535, obs_cap outside 2..GFPL_LM_MAX_OBS.  The context cannot be
+ * destroyed while the object lives.                                                             */
+int  gfpl_kfmap_create(gfpl_ctx* ctx, const gfpl_kfmap_caps* caps, gfpl_kfmap** out);
+int  gfpl_kfmap_destroy(gfpl_kfmap* m);
+/* n_kf (map_keyframes.size()) and the next ids (max_pt_idx, max_ls_idx); any may be NULL. */
+int  gfpl_kfmap_counts(const gfpl_kfmap* m, int32_t* n_kf, int32_t* next_pt, int32_t* next_ls);
+/* The first call is initialize's keyframe (:63-67, :88-92), a later one expandGraphs, max_kf_idx++,
+ * local = true, the index reset and the list insertion of addKeyFrame (:116-134, :147-150).  The new
+ * keyframe has n_pt / n_ls rows, all -1, and owns nothing.  GFPL_E_CAPACITY beyond kf_cap / pt_rows /
+ * ls_rows, GFPL_E_INVALID for a negative count.                                                 */
+int  gfpl_kfmap_add_keyframe(gfpl_kfmap* m, int n_pt, int n_ls, int32_t* kf_idx);
+/* The loop body of lookForCommonMatches' keyframe-pair stage (:266-336, :404-485, has_refinement ==
+ * false) over pairs (kf0 row, kf1 row) as gfpl_kf_common_matches returns them.  A kf0 row with idx
+ * -1 creates a landmark: id = *first_new + its rank among the creating pairs in pair order, both rows'
+ * idx set, kf_obs = [kf0, kf1], owner kf0, inlier, not local (KM9), full_graph[kf0][kf1] and its
+ * mirror + 1.  A row carrying an alive landmark sets kf1's row, appends kf1 and adds 1 to
+ * full_graph[kf1][o] and its mirror for every entry o != kf1 the list held before the call (two kf0
+ * rows may carry one landmark: it receives kf1 twice).  A row carrying a freed landmark does nothing
+ * and lm_out is -1 (:308, KM6).  lm_out[i] is pair i's landmark, created iff >= *first_new.
+ * GFPL_E_INVALID: a NULL pointer, n < 0, kind outside 0..1, kf0 == kf1, a keyframe out of range or
+ * erased, n above either keyframe's rows, a pair row outside its keyframe's rows, a column of pairs
+ * that holds a value twice (KM8), a carried id < -1 or >= the next id.  GFPL_E_CAPACITY: a list
+ * beyond obs_cap, an id beyond the landmark cap.  Bad device data is never used as an index.    */
+int  gfpl_kfmap_observe_pairs(gfpl_kfmap* m, int kind, int kf0, int kf1, const int32_t* pairs /*DEVICE [n][2]*/, int n,
+                              int32_t* lm_out /*DEVICE [n]*/, int32_t* first_new, int32_t* n_new);
+/* The local-map stage's body (:609-624, :745-764) over pairs (row of the caller's map view, row among
+ * kf1's unmatched) as gfpl_kf_local_map_matches returns them: the landmark is sel_ids[p0], the kf1 row
+ * unm_rows[p1]; then the append and graph update of an existing landmark above.  lm_out[i] is the
+ * landmark.  GFPL_E_INVALID also for p0 outside [0, n_sel), p1 outside [0, n_unm), a sel_ids entry that
+ * is not an alive landmark, an unm_rows entry outside kf1's rows; a repeated value in a column of
+ * pairs as above, and n > min(n_sel, n_unm) therefore; n_sel above the kind's next id, n_unm above
+ * kf1's rows, an unm_rows value that two pairs name.                                             */
+int  gfpl_kfmap_observe_local(gfpl_kfmap* m, int kind, int kf1, const int32_t* pairs /*DEVICE [n][2]*/, int n,
+                              const int32_t* sel_ids /*DEVICE [n_sel]*/, int n_sel,
+                              const int32_t* unm_rows /*DEVICE [n_unm]*/, int n_unm, int32_t* lm_out /*DEVICE [n]*/);
+/* formLocalMap (:789-857): every local flag reset; the newest keyframe (back()) local; keyframe i below
+ * it local when full_graph[newest][i] >= min_lm_cov_graph or newest - i <= min_kf_local_map; the alive
+ * landmarks on a local keyframe's rows local.  An erased keyframe i is skipped (KM1).  GFPL_E_STATE
+ * without a keyframe or with the newest erased.                                                 */
+int  gfpl_kfmap_form_local_map(gfpl_kfmap* m, const gfpl_kfmap_params* prm);
+/* The landmarks of `which` in map order (ascending id); ids holds up to the kind's next id.  kf1 is
+ * read for GFPL_KFMAP_LOCAL_UNSEEN only.                                                        */
+int  gfpl_kfmap_select(gfpl_kfmap* m, int kind, int which, int kf1, int32_t* ids /*DEVICE*/, int32_t* n);
+/* kf's rows with idx == -1, in row order (:539-546, :666-673); rows holds up to the keyframe's rows. */
+int  gfpl_kfmap_unmatched(gfpl_kfmap* m, int kind, int kf, int32_t* rows /*DEVICE*/, int32_t* n);
+/* alive && local && kf_idx != 0, ascending (:1115-1127); kf_list holds up to kf_cap. */
+int  gfpl_kfmap_local_keyframes(gfpl_kfmap* m, int32_t* kf_list /*HOST*/, int32_t* n);
+/* removeBadMapLandmarks (:2550-2630): an alive landmark that is not local, with max_kf_idx -
+ * kf_obs[0] > cull_age (KM7) and (!inlier or n_obs < min_lm_obs (KM4)) is removed: the first (lowest)
+ * row of keyframe kf_obs[0] that carries its id becomes -1, owner becomes -1 when it is kf_obs[0],
+ * the landmark is freed.  Rows of other keyframes keep the id (KM5).  A landmark whose kf_obs[0] is
+ * an erased keyframe is skipped (KM2).  The removed ids in map order, ready for GFPL_LM_FREE ops;
+ * each list holds up to the kind's next id.                                                     */
+int  gfpl_kfmap_remove_bad(gfpl_kfmap* m, const gfpl_kfmap_params* prm, int32_t* pt_removed /*DEVICE*/, int32_t* n_pt,
+                           int32_t* ls_removed /*DEVICE*/, int32_t* n_ls);
+/* inlier = value of the listed landmarks (freed ones are passed over); GFPL_E_INVALID for an id
+ * outside [0, next id) or a value outside 0..1.                                                  */
+int  gfpl_kfmap_set_inlier(gfpl_kfmap* m, int kind, const int32_t* ids /*DEVICE [n]*/, int n, int value);
+/* map_keyframes[kf] = NULL and the zeroed graph row and column (:2777-2784); nothing else of
+ * removeRedundantKFs, which the reference disables.                                             */
+int  gfpl_kfmap_erase_keyframe(gfpl_kfmap* m, int kf);
+/* Read and patch, HOST arrays.  Reads take any keyframe below n_kf (erased ones too) and ids below the
+ * cap; outputs may be NULL.  Writes are checked on the host (GFPL_E_INVALID): an alive keyframe, rows
+ * within its rows, idx values in [-1, next id); flags 0 / 1, n_obs in [1, obs_cap] for an alive
+ * landmark and [0, obs_cap] for a freed one, the first n_obs entries of kf_obs below n_kf, owner in
+ * [-1, n_kf), ids below the cap.  write_landmarks takes every array and raises the kind's next id
+ * to id0 + n when that is larger (the ids between are freed landmarks).                         */
+int  gfpl_kfmap_read_keyframe(gfpl_kfmap* m, int kf, gfpl_kfmap_kf* rec, int32_t* pt_idx /*[pt_rows]*/, int32_t* ls_idx /*[ls_rows]*/);
+int  gfpl_kfmap_write_keyframe_idx(gfpl_kfmap* m, int kind, int kf, int row0, int n, const int32_t* idx);
+int  gfpl_kfmap_read_landmarks(gfpl_kfmap* m, int kind, int id0, int n, uint8_t* alive, uint8_t* local, uint8_t* inlier,
+                               int32_t* n_obs, int32_t* owner, int32_t* kf_obs /*[n][obs_cap]*/);
+int  gfpl_kfmap_write_landmarks(gfpl_kfmap* m, int kind, int id0, int n, const uint8_t* alive, const uint8_t* local,
+                                const uint8_t* inlier, const int32_t* n_obs, const int32_t* owner, const int32_t* kf_obs);
+/* The graph in the shape gfpl_pgo_problem takes, HOST arrays (any kind's three may be NULL together):
+ * alive [n_kf], full_graph [n_kf][n_kf], *_kf_start [n_kf + 1], *_kf_idx [up to the next id]: every
+ * landmark with an owner under its owner in ascending id, *_freed [next id].                    */
+int  gfpl_kfmap_export_graph(gfpl_kfmap* m, uint8_t* alive, int32_t* full_graph, int32_t* pt_kf_start, int32_t* pt_kf_idx,
+                             uint8_t* pt_freed, int32_t* ls_kf_start, int32_t* ls_kf_idx, uint8_t* ls_freed);
+/* Instrumentation (tools/bench_kfmap.py): device milliseconds between the first and the last kernel of
+ * the object's last call that launched any; GFPL_E_STATE when there is none.                     */
+int  gfpl_kfmap_debug_ms(gfpl_kfmap* m, float* ms);
+
 /* ------------------------------------- loop-closure candidate search ----- */
 /* DBoW2 as MapHandler uses it (insertKFBowVectorP / L / PL, src/mapHandler.cpp:2865-3000, and
  * lookForLoopCandidates, :3002-3076): TemplatedVocabulary<FORB>::transform and L1Scoring::score
