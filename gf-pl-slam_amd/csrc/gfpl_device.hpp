@@ -1033,6 +1033,23 @@ GFPL_DEV int block_exclusive_scan(int v, int* lds /* >= BLOCK/64 + 1 ints */, in
     return r;
 }
 
+// exclusive scan of tile[0, nt) in place, the total to tile[nt]; one workgroup (the middle launch of an
+// ordered compaction as reduce, scan, scatter: k_kfmap.hip, k_mapgeo.hip)
+template <int BLOCK>
+GFPL_DEV int scan_tiles(int32_t* tile, int nt, int* scan) {
+    int carry = 0;
+    for (int b0 = 0; b0 < nt; b0 += BLOCK) {
+        const int b = b0 + threadIdx.x;
+        const int v = b < nt ? tile[b] : 0;
+        int total;
+        const int ex = block_exclusive_scan<BLOCK>(v, scan, &total);
+        if (b < nt) tile[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) tile[nt] = carry;
+    return carry;
+}
+
 // ------------------------------------------------------------ phase clock --
 // Diagnostic builds time a kernel's phases into its sequences' debug slots (DevScratch::dbg; what each
 // slot means under each flag: gfpl_records.hpp).  One compile flag per instrumented kernel:

@@ -84,4 +84,23 @@ int ba_read_system(const Ptrs& m, const gfpl_lba_counts& n, const gfpl_lba_resul
     return GFPL_OK;
 }
 
+// what gfpl_mapgeo.cpp reads of the objects it works beside.
+// gfpl_kfmap.cpp: a map's index half as the last call left it (device arrays, host counts)
+struct KfMapDevice {
+    gfpl_ctx* ctx;
+    gfpl_kfmap_caps caps;
+    KfMapCore core;
+    KfMapLm lm[2];
+    bool failed;
+};
+KfMapDevice kfmap_device(const gfpl_kfmap* m);
+// gfpl_lba.cpp: gfpl_lba_solve after its staging, for one problem whose index arrays the caller writes
+// on the device.  lba_stage_device checks p's counts against the object (GFPL_E_CAPACITY), makes record
+// 0 from p and returns it: the caller enqueues the kernel that fills q->lm_start / obs_lm / obs_kf, then
+// lba_enqueue uploads the records, launches the solve and copies n results to the host.  Nothing here
+// synchronises.
+gfpl_ctx* lba_ctx(const gfpl_lba* l);
+int lba_stage_device(gfpl_lba* l, const gfpl_lba_problem& p, LbaProb* q);
+hipError_t lba_enqueue(gfpl_lba* l, int n, int lds_kfs, const gfpl_lba_params* prm, gfpl_lba_result* results, hipStream_t s);
+
 }  // namespace gfpl

@@ -304,6 +304,48 @@ hipError_t enqueue_kfmap_remove_bad(const KfMapCore& c, const KfMapLm& L, const 
 hipError_t enqueue_kfmap_set_inlier(const KfMapCore& c, const KfMapLm& L, const int32_t* ids, int n, int value, hipStream_t s);
 hipError_t enqueue_kfmap_erase_keyframe(const KfMapCore& c, int kf, hipStream_t s);
 
+// the map's geometry half (k_mapgeo.hip); all pointers device.  The arrays are MapGeoMem's: MapGeoLm one
+// kind's state, MapGeoCore the keyframes, the header and the observe calls' workspace.
+struct MapGeoLm {
+    double *lm3d, *obs, *sigma;   // [cap][lw], [cap][obs_cap][ow], [cap][obs_cap]
+    int32_t* nobs;
+    int lw, ow, cap;
+};
+struct MapGeoCore {
+    int32_t* hdr;                 // MAPGEO_H_*
+    double *T_kf, *x_kf;
+    int32_t *pend, *pair_n0;
+    int kf_cap, obs_cap;
+};
+// one observe call: kf0 >= 0 the keyframe-pair stage, kf0 < 0 the local-map stage (pairs' column 1 is a
+// row of unm_rows).  g0 / g1: the 3D geometry of kf0's rows (P, or sP and eP) and the observation of
+// either keyframe's rows (pl or le); n0 / n1 the views' rows.
+struct MapGeoObserve {
+    int kf0, n, n_unm, first_new, n0, n1;
+    const int32_t *pairs, *unm_rows, *lm_out;
+    const double *P0, *Q0, *o0, *o1;
+};
+// one assembly.  The kfmap's arrays are read only.  which: GFPL_KFMAP_LOCAL or GFPL_KFMAP_ALIVE
+struct MapGeoAsm {
+    int which, n_kf, next[2];
+    const uint8_t *kf_alive, *kf_local;
+    const uint8_t *lm_alive[2], *lm_local[2];
+    const int32_t *k_nobs[2], *k_obs[2];   // the kfmap's n_obs and kf_obs [cap][obs_cap]
+    int32_t *kf_slot, *kf_mark, *kf_list, *fix_list;
+    int32_t *lm_cnt[2], *tile_lm[2], *tile_obs[2], *lm_list[2], *lm_off[2];
+    double *a_x_kf, *a_T_kf, *a_T_fix, *a_lm3d[2], *a_obs[2], *a_sigma[2];
+    int32_t *a_obs_lm[2], *a_obs_kf[2];
+};
+hipError_t enqueue_mapgeo_observe(const MapGeoCore& c, const MapGeoLm& L, const MapGeoObserve& a, hipStream_t s);
+hipError_t enqueue_mapgeo_free(const MapGeoCore& c, const MapGeoLm& L, const int32_t* ids, int n, hipStream_t s);
+hipError_t enqueue_mapgeo_assemble(const MapGeoCore& c, const MapGeoLm& pt, const MapGeoLm& ls, const MapGeoAsm& a, hipStream_t s);
+// an assembled problem's index arrays over the LBA's unified numbering (LbaMem: lm_start, obs_lm, obs_kf)
+hipError_t enqueue_mapgeo_lba_index(const MapGeoAsm& a, const gfpl_lba_counts& n, int32_t* lm_start, int32_t* obs_lm, int32_t* obs_kf,
+                                    hipStream_t s);
+// :1688-1712: the solved poses and landmarks of an assembled problem back into the store
+hipError_t enqueue_mapgeo_write_back(const MapGeoCore& c, const MapGeoLm& pt, const MapGeoLm& ls, const MapGeoAsm& a,
+                                     const gfpl_lba_counts& n, hipStream_t s);
+
 }  // namespace gfpl
 
 namespace gfpl {

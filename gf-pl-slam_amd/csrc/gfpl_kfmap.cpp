@@ -113,6 +113,10 @@ hipError_t put_dev(hipError_t e, T* dst, const T* src, size_t n, hipStream_t s) 
 
 }  // namespace
 
+namespace gfpl {
+KfMapDevice kfmap_device(const gfpl_kfmap* m) { return KfMapDevice{m->ctx, m->caps, core_of(m), {lm_of(m, 0), lm_of(m, 1)}, m->failed}; }
+}  // namespace gfpl
+
 extern "C" {
 
 void gfpl_default_kfmap_params(gfpl_kfmap_params* prm) {

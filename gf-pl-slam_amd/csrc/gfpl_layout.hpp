@@ -553,4 +553,58 @@ struct KfMapMem {
         : c{0, base}, kf_cap(kf_cap), rows{pt_rows, ls_rows}, lm_cap{pt_lm_cap, ls_lm_cap}, obs_cap(obs_cap) {}
 };
 
+// ---- the map's geometry half (gfpl_mapgeo, k_mapgeo.hip, gfpl_mapgeo.cpp), ids and caps gfpl_kfmap's:
+// per keyframe T_kf_w and x_kf_w; per landmark and kind its 3D geometry, obs_list and sigma_list at a
+// fixed stride of obs_cap with their length; then the calls' header, the observe calls' workspace and
+// the buffers gfpl_mapgeo_assemble fills (a gfpl_lba_problem's arrays at the caps, a_*).  Landmark
+// arrays are [2] by kind; a kind's 3D geometry is MAPGEO_LM_W doubles, an observation MAPGEO_OBS_W.
+constexpr int MAPGEO_HDR = 16;       // int32 words of the header (MAPGEO_H_*), zeroed when a call starts, copied to the host once per call
+enum { MAPGEO_H_ERR = 0, MAPGEO_H_NKF, MAPGEO_H_NFIX, MAPGEO_H_NPT, MAPGEO_H_NLS, MAPGEO_H_NPTOBS, MAPGEO_H_NLSOBS };
+constexpr int MAPGEO_LM_W[2] = {3, 6}, MAPGEO_OBS_W[2] = {2, 3};
+constexpr int MAPGEO_SLOT_NONE = INT32_MIN;   // kf_slot of a keyframe that is neither listed nor fixed
+struct MapGeoMem {
+    Carver c;
+    int kf_cap, rows[2], lm_cap[2], obs_cap;
+    size_t max_rows = (size_t)(rows[0] > rows[1] ? rows[0] : rows[1]);
+    size_t max_lm = (size_t)(lm_cap[0] > lm_cap[1] ? lm_cap[0] : lm_cap[1]);
+    size_t n_tiles = (max_lm + KFMAP_TILE - 1) / KFMAP_TILE;
+    size_t lm_obs[2] = {(size_t)lm_cap[0] * obs_cap, (size_t)lm_cap[1] * obs_cap};
+    int32_t* hdr = c.take<int32_t>(MAPGEO_HDR);
+    double* T_kf = c.take<double>((size_t)kf_cap * 16);
+    double* x_kf = c.take<double>((size_t)kf_cap * 6);
+    double* lm3d[2] = {c.take<double>((size_t)lm_cap[0] * MAPGEO_LM_W[0]), c.take<double>((size_t)lm_cap[1] * MAPGEO_LM_W[1])};
+    int32_t* nobs[2] = {c.take<int32_t>((size_t)lm_cap[0]), c.take<int32_t>((size_t)lm_cap[1])};
+    double* obs[2] = {c.take<double>(lm_obs[0] * MAPGEO_OBS_W[0]), c.take<double>(lm_obs[1] * MAPGEO_OBS_W[1])};
+    double* sigma[2] = {c.take<double>(lm_obs[0]), c.take<double>(lm_obs[1])};
+    // the observe calls.  pend: pairs a landmark receives within the running call (all 0 between calls);
+    // pair_n0: per pair its landmark's list length before the call.
+    int32_t* pend = c.take<int32_t>(max_lm);
+    int32_t* pair_n0 = c.take<int32_t>(max_rows);
+    // assemble.  kf_slot: a keyframe's slot (>= 0 listed, < 0 fixed, MAPGEO_SLOT_NONE); kf_mark: named by a
+    // selected landmark; lm_cnt: a landmark's observations that go into the problem (0: not selected);
+    // tile_lm / tile_obs: per kind the tile sums of the selected landmarks and of their observations,
+    // then their exclusive scans in place; lm_off: first observation of each selected landmark.
+    int32_t* kf_slot = c.take<int32_t>((size_t)kf_cap);
+    int32_t* kf_mark = c.take<int32_t>((size_t)kf_cap);
+    int32_t* kf_list = c.take<int32_t>((size_t)kf_cap);
+    int32_t* fix_list = c.take<int32_t>((size_t)kf_cap);
+    int32_t* lm_cnt[2] = {c.take<int32_t>((size_t)lm_cap[0]), c.take<int32_t>((size_t)lm_cap[1])};
+    int32_t* tile_lm[2] = {c.take<int32_t>(n_tiles + 1), c.take<int32_t>(n_tiles + 1)};
+    int32_t* tile_obs[2] = {c.take<int32_t>(n_tiles + 1), c.take<int32_t>(n_tiles + 1)};
+    int32_t* lm_list[2] = {c.take<int32_t>((size_t)lm_cap[0]), c.take<int32_t>((size_t)lm_cap[1])};
+    int32_t* lm_off[2] = {c.take<int32_t>((size_t)lm_cap[0] + 1), c.take<int32_t>((size_t)lm_cap[1] + 1)};
+    double* a_x_kf = c.take<double>((size_t)kf_cap * 6);
+    double* a_x_out = c.take<double>((size_t)kf_cap * 6);
+    double* a_T_kf = c.take<double>((size_t)kf_cap * 16);
+    double* a_T_fix = c.take<double>((size_t)kf_cap * 16);
+    double* a_lm3d[2] = {c.take<double>((size_t)lm_cap[0] * MAPGEO_LM_W[0]), c.take<double>((size_t)lm_cap[1] * MAPGEO_LM_W[1])};
+    double* a_obs[2] = {c.take<double>(lm_obs[0] * MAPGEO_OBS_W[0]), c.take<double>(lm_obs[1] * MAPGEO_OBS_W[1])};
+    double* a_sigma[2] = {c.take<double>(lm_obs[0]), c.take<double>(lm_obs[1])};
+    int32_t* a_obs_lm[2] = {c.take<int32_t>(lm_obs[0]), c.take<int32_t>(lm_obs[1])};
+    int32_t* a_obs_kf[2] = {c.take<int32_t>(lm_obs[0]), c.take<int32_t>(lm_obs[1])};
+    size_t bytes = (c.off + 255) & ~(size_t)255;
+    MapGeoMem(char* base, int kf_cap, int pt_rows, int ls_rows, int pt_lm_cap, int ls_lm_cap, int obs_cap)
+        : c{0, base}, kf_cap(kf_cap), rows{pt_rows, ls_rows}, lm_cap{pt_lm_cap, ls_lm_cap}, obs_cap(obs_cap) {}
+};
+
 }  // namespace gfpl

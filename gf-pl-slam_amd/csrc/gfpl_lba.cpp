@@ -44,6 +44,46 @@ int check_list(const int32_t* lm, const int32_t* kf, int n_obs, int n_lm, int n_
 
 }  // namespace
 
+namespace gfpl {
+
+gfpl_ctx* lba_ctx(const gfpl_lba* l) { return l->ctx; }
+
+int lba_stage_device(gfpl_lba* l, const gfpl_lba_problem& p, LbaProb* q) {
+    const gfpl_lba_counts& c = p.n;
+    if (c.n_kf > l->caps.n_kf || c.n_pt > l->caps.n_pt || c.n_ls > l->caps.n_ls || c.n_pt_obs > l->caps.n_pt_obs ||
+        c.n_ls_obs > l->caps.n_ls_obs)
+        return GFPL_E_CAPACITY;
+    const LbaMem m(l->base, c.n_kf, c.n_pt, c.n_ls, c.n_pt_obs + c.n_ls_obs);
+    LbaProb& h = *reinterpret_cast<LbaProb*>(l->stage);
+    std::memset(&h, 0, sizeof h);
+    h.n = c;
+    ba_fill_prob(h, p);
+    h.lm_start = m.lm_start; h.obs_lm = m.obs_lm; h.obs_kf = m.obs_kf;
+    h.m = m.p;
+    l->last.assign(1, h);
+    *q = h;
+    return GFPL_OK;
+}
+
+// the staged records to the device, the launch, the results to the host
+hipError_t lba_enqueue(gfpl_lba* l, int n, int lds_kfs, const gfpl_lba_params* prm, gfpl_lba_result* results, hipStream_t s) {
+    hipError_t e = hipMemcpyAsync(l->d_probs, l->stage, (size_t)n * sizeof(LbaProb), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return e;
+    LbaArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.cam = dev_cam(gfpl_ctx_camera(l->ctx));
+    a.homog_th = gfpl_ctx_config(l->ctx)->homog_th;
+    a.prm = *prm;
+    a.probs = l->d_probs;
+    a.out = l->d_res;
+    a.lds_kfs = lds_kfs;
+    e = launch_lba(a, n, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(results, l->d_res, (size_t)n * sizeof(gfpl_lba_result), hipMemcpyDeviceToHost, s);
+    return e;
+}
+
+}  // namespace gfpl
+
 extern "C" {
 
 void gfpl_default_lba_params(gfpl_lba_params* prm) {
@@ -182,24 +222,13 @@ int gfpl_lba_solve(gfpl_lba* l, const gfpl_lba_problem* problems, int n, const g
         start[nlm] = nobs;
         cursor += (o_kf + (size_t)nobs + 63) & ~(size_t)63;
     }
-    hipError_t e = hipMemcpyAsync(l->d_probs, hp, (size_t)n * sizeof(LbaProb), hipMemcpyHostToDevice, s);
+    hipError_t e = hipSuccess;
     for (int i = 0; i < n && e == hipSuccess; ++i) {
         const LbaProb& q = l->last[(size_t)i];
         const size_t cnt = (size_t)(q.obs_kf - q.lm_start) + (size_t)(q.n.n_pt_obs + q.n.n_ls_obs);
         e = hipMemcpyAsync(const_cast<int32_t*>(q.lm_start), hidx[(size_t)i], cnt * sizeof(int32_t), hipMemcpyHostToDevice, s);
     }
-    if (e == hipSuccess) {
-        LbaArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.cam = dev_cam(cam);
-        a.homog_th = gfpl_ctx_config(l->ctx)->homog_th;
-        a.prm = *prm;
-        a.probs = l->d_probs;
-        a.out = l->d_res;
-        a.lds_kfs = lds_kfs;
-        e = launch_lba(a, n, s);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(results, l->d_res, (size_t)n * sizeof(gfpl_lba_result), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = lba_enqueue(l, n, lds_kfs, prm, results, s);
     const hipError_t es = hipStreamSynchronize(s);   // also on an error path: the staging is still in use
     if (e != hipSuccess || es != hipSuccess) {
         l->last.clear();

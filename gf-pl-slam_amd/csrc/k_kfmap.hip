@@ -181,24 +181,9 @@ __global__ void __launch_bounds__(KFMAP_BLOCK) k_kfmap_obs_check(KfMapCore c, Kf
     if (threadIdx.x == 0) c.tile[blockIdx.x] = total;
 }
 
-// exclusive scan of tile[0, nt) in place, the total to tile[nt]; one workgroup
-GFPL_DEV int scan_tiles(int32_t* tile, int nt, int* scan) {
-    int carry = 0;
-    for (int b0 = 0; b0 < nt; b0 += KFMAP_BLOCK) {
-        const int b = b0 + threadIdx.x;
-        const int v = b < nt ? tile[b] : 0;
-        int total;
-        const int ex = block_exclusive_scan<KFMAP_BLOCK>(v, scan, &total);
-        if (b < nt) tile[b] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) tile[nt] = carry;
-    return carry;
-}
-
 __global__ void __launch_bounds__(KFMAP_BLOCK) k_kfmap_obs_scan(KfMapCore c, KfMapLm L, KfMapObserve a, int nt) {
     __shared__ int scan[KFMAP_BLOCK / 64 + 1];
-    const int n_new = scan_tiles(c.tile, nt, scan);
+    const int n_new = scan_tiles<KFMAP_BLOCK>(c.tile, nt, scan);
     if (threadIdx.x != 0) return;
     int err = c.hdr[KFMAP_H_ERR];
     if (n_new > L.cap - L.next) {
@@ -295,7 +280,7 @@ __global__ void __launch_bounds__(KFMAP_BLOCK) k_kfmap_cmp_reduce(KfMapCore c, K
 
 __global__ void __launch_bounds__(KFMAP_BLOCK) k_kfmap_cmp_scan(KfMapCore c, int nt, int slot) {
     __shared__ int scan[KFMAP_BLOCK / 64 + 1];
-    const int total = scan_tiles(c.tile, nt, scan);
+    const int total = scan_tiles<KFMAP_BLOCK>(c.tile, nt, scan);
     if (threadIdx.x == 0) c.hdr[slot] = total;
 }
 

@@ -739,6 +739,22 @@ def hiplib() -> C.CDLL:
             "gfpl_kfmap_write_landmarks": ([P, C.c_int, C.c_int, C.c_int, P, P, P, P, P, P], C.c_int),
             "gfpl_kfmap_export_graph": ([P, P, P, P, P, P, P, P, P], C.c_int),
             "gfpl_kfmap_debug_ms": ([P, P], C.c_int),
+            "gfpl_mapgeo_bytes": ([P], C.c_int64),
+            "gfpl_mapgeo_create": ([P, P, C.POINTER(P)], C.c_int),
+            "gfpl_mapgeo_destroy": ([P], C.c_int),
+            "gfpl_mapgeo_set_keyframe": ([P, C.c_int, P, P], C.c_int),
+            "gfpl_mapgeo_read_keyframe": ([P, C.c_int, P, P], C.c_int),
+            "gfpl_mapgeo_arrays": ([P, P, P, P, P], C.c_int),
+            "gfpl_mapgeo_observe_pairs": ([P, C.c_int, C.c_int, C.c_int, P, P, P, P, C.c_int, C.c_int], C.c_int),
+            "gfpl_mapgeo_observe_local": ([P, C.c_int, C.c_int, P, P, C.c_int, P, C.c_int, P], C.c_int),
+            "gfpl_mapgeo_free": ([P, C.c_int, P, C.c_int], C.c_int),
+            "gfpl_mapgeo_read_landmarks": ([P, C.c_int, C.c_int, C.c_int, P, P, P, P], C.c_int),
+            "gfpl_mapgeo_write_landmarks": ([P, C.c_int, C.c_int, C.c_int, P, P, P, P], C.c_int),
+            "gfpl_mapgeo_assemble": ([P, P, C.c_int, P, P], C.c_int),
+            "gfpl_mapgeo_assembled_ids": ([P, P, P, P, P], C.c_int),
+            "gfpl_mapgeo_read_assembled": ([P, P, P, P, P, P], C.c_int),
+            "gfpl_mapgeo_lba": ([P, P, P, P, P, P], C.c_int),
+            "gfpl_mapgeo_debug_ms": ([P, P], C.c_int),
             "gfpl_default_gba_params": ([P], None),
             "gfpl_gba_check": ([P, P], C.c_int),
             "gfpl_gba_workspace": ([P, P, P], C.c_int),
@@ -2087,6 +2103,201 @@ class KeyframeMap:
     def close(self):
         if getattr(self, "h", None):
             check(self.L.gfpl_kfmap_destroy(self.h), "kfmap_destroy")
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MapGeoLists(C.Structure):
+    """gfpl_mapgeo_lists: HOST copies of an assembled problem's four index lists."""
+    _fields_ = [(k, _vp) for k in ("pt_obs_lm", "pt_obs_kf", "ls_obs_lm", "ls_obs_kf")] + [
+        ("cap_pt_obs", C.c_int32), ("cap_ls_obs", C.c_int32)]
+
+
+def mapgeo_bytes(caps: KfMapCaps) -> int:
+    """gfpl_mapgeo_bytes (host only): device bytes of an object with these caps, -1 for caps it refuses."""
+    return int(hiplib().gfpl_mapgeo_bytes(C.byref(caps)))
+
+
+class MapGeoView:
+    """The arrays of a gfpl_kf_view that gfpl_mapgeo reads, on the device: P / pl [n_pt][3] / [n_pt][2]
+    and sP / eP / le [n_ls][3] (numpy float64 or None)."""
+
+    def __init__(self, device, P=None, pl=None, sP=None, eP=None, le=None):
+        import torch
+        self.s = KFViewStruct()
+        self.keep = {}
+        for k, v, w in (("P", P, 3), ("pl", pl, 2), ("sP", sP, 3), ("eP", eP, 3), ("le", le, 3)):
+            if v is None:
+                continue
+            a = np.ascontiguousarray(np.asarray(v, np.float64).reshape(-1, w))
+            self.keep[k] = torch.from_numpy(a.copy()).to(device) if len(a) else None
+            setattr(self.s, k, _ptr(self.keep[k]))
+            if k == "pl":
+                self.s.n_pt = len(a)
+            if k == "le":
+                self.s.n_ls = len(a)
+        torch.cuda.synchronize()
+
+
+class MapGeometry:
+    """gfpl_mapgeo: the geometry half of one map on the device (T_kf_w / x_kf_w of every keyframe,
+    point3D / line3D, obs_list and sigma_list of every landmark), beside a KeyframeMap of the same caps
+    and indexed by its ids.  Views are MapGeoView or KeyFrameView objects with device arrays; device
+    lists are torch int32 tensors; the *_rc methods return the C code, the others raise GfplError."""
+
+    LM_W, OBS_W = (3, 6), (2, 3)
+
+    def __init__(self, ctx: "Context", kf_cap: int, pt_rows: int, ls_rows: int, pt_lm_cap: int, ls_lm_cap: int, obs_cap: int):
+        self.ctx, self.L = ctx, ctx.L
+        self.caps = KfMapCaps(kf_cap, pt_rows, ls_rows, pt_lm_cap, ls_lm_cap, obs_cap)
+        self.h = C.c_void_p()
+        check(self.L.gfpl_mapgeo_create(ctx.h, C.byref(self.caps), C.byref(self.h)), "mapgeo_create")
+
+    def _dev(self):
+        import torch
+        return torch.device("cuda", self.ctx.device)
+
+    def _in(self, a, cols: int = 0):
+        import torch
+        if not isinstance(a, torch.Tensor):
+            a = np.ascontiguousarray(a, np.int32)
+            a = a.reshape(-1, cols) if cols else a.reshape(-1)
+            a = torch.from_numpy(a.copy()).to(self._dev())
+        torch.cuda.synchronize()
+        return a
+
+    def view(self, **arrays) -> MapGeoView:
+        return MapGeoView(self._dev(), **arrays)
+
+    def set_keyframe_rc(self, kf: int, T_kf_w, x_kf_w) -> int:
+        T = np.ascontiguousarray(np.asarray(T_kf_w, np.float64).reshape(16))
+        x = np.ascontiguousarray(np.asarray(x_kf_w, np.float64).reshape(6))
+        return self.L.gfpl_mapgeo_set_keyframe(self.h, int(kf), _ptr(T), _ptr(x))
+
+    def set_keyframe(self, kf: int, T_kf_w, x_kf_w) -> None:
+        check(self.set_keyframe_rc(kf, T_kf_w, x_kf_w), "mapgeo_set_keyframe")
+
+    def read_keyframe(self, kf: int):
+        """(T_kf_w [4][4], x_kf_w [6])"""
+        T, x = np.zeros(16), np.zeros(6)
+        check(self.L.gfpl_mapgeo_read_keyframe(self.h, int(kf), _ptr(T), _ptr(x)), "mapgeo_read_keyframe")
+        return T.reshape(4, 4), x
+
+    def arrays(self) -> dict:
+        """the device addresses of T_kf, x_kf, point3D, line3D (ints)"""
+        v = [C.c_void_p() for _ in range(4)]
+        check(self.L.gfpl_mapgeo_arrays(self.h, *[C.byref(x) for x in v]), "mapgeo_arrays")
+        return dict(zip(("T_kf", "x_kf", "point3D", "line3D"), [x.value for x in v]))
+
+    def observe_pairs_rc(self, kind: int, kf0: int, kf1: int, v0, v1, pairs, lm_out, first_new: int) -> int:
+        p, out = self._in(pairs, 2), self._in(lm_out)
+        return self.L.gfpl_mapgeo_observe_pairs(self.h, int(kind), int(kf0), int(kf1), C.byref(v0.s), C.byref(v1.s), _ptr(p),
+                                                _ptr(out), int(p.shape[0]), int(first_new))
+
+    def observe_pairs(self, kind: int, kf0: int, kf1: int, v0, v1, pairs, lm_out, first_new: int) -> None:
+        check(self.observe_pairs_rc(kind, kf0, kf1, v0, v1, pairs, lm_out, first_new), "mapgeo_observe_pairs")
+
+    def observe_local_rc(self, kind: int, kf1: int, v1, pairs, unm_rows, lm_out) -> int:
+        p, unm, out = self._in(pairs, 2), self._in(unm_rows), self._in(lm_out)
+        return self.L.gfpl_mapgeo_observe_local(self.h, int(kind), int(kf1), C.byref(v1.s), _ptr(p), int(p.shape[0]), _ptr(unm),
+                                                int(unm.shape[0]), _ptr(out))
+
+    def observe_local(self, kind: int, kf1: int, v1, pairs, unm_rows, lm_out) -> None:
+        check(self.observe_local_rc(kind, kf1, v1, pairs, unm_rows, lm_out), "mapgeo_observe_local")
+
+    def free_rc(self, kind: int, ids) -> int:
+        t = self._in(ids)
+        return self.L.gfpl_mapgeo_free(self.h, int(kind), _ptr(t), int(t.shape[0]))
+
+    def free(self, kind: int, ids) -> None:
+        check(self.free_rc(kind, ids), "mapgeo_free")
+
+    def read_landmarks(self, kind: int, id0: int, n: int) -> dict:
+        """lm3d [n][3 or 6], n_obs [n], obs [n][obs_cap][2 or 3], sigma [n][obs_cap]"""
+        oc = self.caps.obs_cap
+        d = dict(lm3d=np.zeros((n, self.LM_W[kind])), n_obs=np.zeros(n, np.int32), obs=np.zeros((n, oc, self.OBS_W[kind])),
+                 sigma=np.zeros((n, oc)))
+        check(self.L.gfpl_mapgeo_read_landmarks(self.h, int(kind), int(id0), int(n), *[_ptr(d[k]) for k in
+              ("lm3d", "n_obs", "obs", "sigma")]), "mapgeo_read_landmarks")
+        return d
+
+    def write_landmarks_rc(self, kind: int, id0: int, lm3d, n_obs, obs, sigma) -> int:
+        c = np.ascontiguousarray(n_obs, np.int32).reshape(-1)
+        n, oc = len(c), self.caps.obs_cap
+        a = np.ascontiguousarray(np.asarray(lm3d, np.float64).reshape(n, self.LM_W[kind]))
+        o = np.ascontiguousarray(np.asarray(obs, np.float64).reshape(n, oc, self.OBS_W[kind]))
+        s = np.ascontiguousarray(np.asarray(sigma, np.float64).reshape(n, oc))
+        return self.L.gfpl_mapgeo_write_landmarks(self.h, int(kind), int(id0), n, _ptr(a), _ptr(c), _ptr(o), _ptr(s))
+
+    def write_landmarks(self, kind: int, id0: int, lm3d, n_obs, obs, sigma) -> None:
+        check(self.write_landmarks_rc(kind, id0, lm3d, n_obs, obs, sigma), "mapgeo_write_landmarks")
+
+    def assemble_rc(self, kfmap: "KeyframeMap", which: int, host_lists: bool = True):
+        """(code, LbaProblemStruct, lists): the struct's doubles are the object's device buffers; with
+        host_lists the index lists are numpy arrays (kept in `lists`) cut to the counts."""
+        p = LbaProblemStruct()
+        oc = self.caps.obs_cap
+        keep = None
+        if host_lists:
+            cp, cl = self.caps.pt_lm_cap * oc, self.caps.ls_lm_cap * oc
+            keep = dict(pt_obs_lm=np.full(cp, -9, np.int32), pt_obs_kf=np.full(cp, -9, np.int32),
+                        ls_obs_lm=np.full(cl, -9, np.int32), ls_obs_kf=np.full(cl, -9, np.int32))
+            ls = MapGeoLists(*[_ptr(keep[k]) for k in LBA_INDICES], cp, cl)
+        rc = self.L.gfpl_mapgeo_assemble(self.h, kfmap.h, int(which), C.byref(p), C.byref(ls) if host_lists else None)
+        if rc == 0 and host_lists:
+            keep = {k: v[: (p.n.n_pt_obs if k.startswith("pt") else p.n.n_ls_obs)] for k, v in keep.items()}
+        return rc, p, keep
+
+    def assemble(self, kfmap: "KeyframeMap", which: int, host_lists: bool = True):
+        rc, p, keep = self.assemble_rc(kfmap, which, host_lists)
+        check(rc, "mapgeo_assemble")
+        return p, keep
+
+    def read_assembled(self, p: LbaProblemStruct) -> dict:
+        """gfpl_mapgeo_read_assembled: the last assembly's doubles (x_kf ... ls_sigma) and id lists
+        (kf_list, fix_list, pt_list, ls_list) as numpy arrays of p's counts"""
+        n = p.n
+        h = LbaProblemStruct()
+        out = {}
+        for k, w, cnt in (("x_kf", 6, n.n_kf), ("T_kf", 16, n.n_kf), ("T_fix", 16, n.n_fix), ("pt", 3, n.n_pt), ("ls", 6, n.n_ls),
+                          ("pt_obs", 2, n.n_pt_obs), ("pt_sigma", 1, n.n_pt_obs), ("ls_obs", 3, n.n_ls_obs), ("ls_sigma", 1, n.n_ls_obs)):
+            out[k] = np.zeros((cnt, w))
+            setattr(h, k, _ptr(out[k]) if cnt else None)
+        ids = {k: np.zeros(max(cnt, 1), np.int32) for k, cnt in
+               (("kf_list", n.n_kf), ("fix_list", n.n_fix), ("pt_list", n.n_pt), ("ls_list", n.n_ls))}
+        check(self.L.gfpl_mapgeo_read_assembled(self.h, C.byref(h), *[_ptr(v) for v in ids.values()]), "mapgeo_read_assembled")
+        for k, cnt in (("kf_list", n.n_kf), ("fix_list", n.n_fix), ("pt_list", n.n_pt), ("ls_list", n.n_ls)):
+            out[k] = ids[k][:cnt]
+        return out
+
+    def lba_rc(self, kfmap: "KeyframeMap", solver: "LbaSolver", params: Optional[LbaParams] = None):
+        """(code, LbaResult, LbaCounts): gfpl_mapgeo_lba on an open LbaSolver of the same context"""
+        prm = params if params is not None else LbaParams.default()
+        res, cnt = LbaResult(), LbaCounts()
+        rc = self.L.gfpl_mapgeo_lba(self.h, kfmap.h, solver.h, C.byref(prm), C.byref(res), C.byref(cnt))
+        return rc, res, cnt
+
+    def lba(self, kfmap: "KeyframeMap", solver: "LbaSolver", params: Optional[LbaParams] = None):
+        rc, res, cnt = self.lba_rc(kfmap, solver, params)
+        check(rc, "mapgeo_lba")
+        return res, cnt
+
+    def nbytes(self) -> int:
+        return mapgeo_bytes(self.caps)
+
+    def last_device_ms(self) -> float:
+        ms = C.c_float(0.0)
+        check(self.L.gfpl_mapgeo_debug_ms(self.h, C.byref(ms)), "mapgeo_debug_ms")
+        return float(ms.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            check(self.L.gfpl_mapgeo_destroy(self.h), "mapgeo_destroy")
             self.h = None
 
     def __del__(self):

@@ -1197,6 +1197,105 @@ int  gfpl_gba_solve(gfpl_gba* gba, const gfpl_lba_problem* problems, int n, cons
 int  gfpl_gba_debug_system(gfpl_gba* gba, int i, int iteration, double* U, double* g, double* V_pt, double* V_ls,
                            double* W_pt, double* W_ls, int32_t* pairs, double* err);
 
+/* ------------------------------------- the map's geometry half ---------- */
+/* What MapPoint / MapLine / KeyFrame hold beside the indices and the descriptors, as a third device
+ * object per map (k_mapgeo.hip, gfpl_mapgeo.cpp, DESIGN.md §4n, ledger MG1-MG7), created with the
+ * gfpl_kfmap's caps and indexed by its ids: per keyframe T_kf_w [kf_cap][16] and x_kf_w [kf_cap][6]
+ * (gfpl_pgo_problem's T_kf / x_kf layout), per landmark point3D [pt_lm_cap][3] / line3D
+ * [ls_lm_cap][6] (gfpl_pgo_problem's pt / ls layout), n_obs, obs_list at a stride of obs_cap (2
+ * doubles per point observation: pl; 3 per line observation: le) and sigma_list at the same stride.
+ * Entry i of a landmark's obs / sigma belongs to entry i of the gfpl_kfmap's kf_obs: after a pair of
+ * matching calls on the two objects their n_obs agree.  dir_list, pts_list and med_obs_dir are not
+ * kept (nothing on this path reads them); desc_list is gfpl_lmstore's.
+ * The contract is gfpl_kfmap's: host checks first; one synchronisation per call unless stated; a
+ * refused call changes nothing; bad device data is never used as an index; GFPL_E_INVALID wins over
+ * GFPL_E_CAPACITY; GFPL_E_STATE from every call after a GFPL_E_HIP.                              */
+typedef struct gfpl_mapgeo gfpl_mapgeo;
+/* Host only: the device bytes of an object with these caps, -1 for caps gfpl_kfmap_create refuses. */
+int64_t gfpl_mapgeo_bytes(const gfpl_kfmap_caps* caps);
+/* Every n_obs 0, every double 0.  The context cannot be destroyed while the object lives.          */
+int  gfpl_mapgeo_create(gfpl_ctx* ctx, const gfpl_kfmap_caps* caps, gfpl_mapgeo** out);
+int  gfpl_mapgeo_destroy(gfpl_mapgeo* g);
+/* addKeyFrame storing the tracker's pose: T_kf_w [16] and x_kf_w [6], HOST doubles; kf in [0, kf_cap). */
+int  gfpl_mapgeo_set_keyframe(gfpl_mapgeo* g, int kf, const double* T_kf_w, const double* x_kf_w);
+int  gfpl_mapgeo_read_keyframe(gfpl_mapgeo* g, int kf, double* T_kf_w, double* x_kf_w);   /* HOST; either may be NULL */
+/* The DEVICE arrays of the store, fixed for its lifetime (any may be NULL): gfpl_pgo_solve and
+ * gfpl_map_fuse_search work on them in place.  No synchronisation.                                 */
+int  gfpl_mapgeo_arrays(gfpl_mapgeo* g, double** T_kf, double** x_kf, double** point3D, double** line3D);
+/* The geometry half of lookForCommonMatches' keyframe-pair loop body (src/mapHandler.cpp:270-335,
+ * :407-480).  pairs, lm_out and first_new are what gfpl_kfmap_observe_pairs took and returned; v0 / v1
+ * are kf0's / kf1's views with DEVICE arrays, of which kind 0 reads P and pl, kind 1 sP, eP and le
+ * (v0's 3D arrays, both views' observations).  A created landmark (lm_out[i] >= first_new) gets
+ * point3D = T_kf_w(kf0) P0 (line3D = [T sP0, T eP0]) with the STORE's pose of kf0, obs = [pl0, pl1]
+ * ([le0, le1]), sigma = [1, 1] (the constructor's and addMap*Observation's default), n_obs = 2.  A
+ * carried landmark appends pl1 / le1 and 1.0 at place n_obs before the call + the number of pairs
+ * j < i with lm_out[j] == lm_out[i]: the reference's order when two kf0 rows carry one landmark.
+ * lm_out[i] == -1 does nothing (:308).
+ * GFPL_E_INVALID: a NULL pointer, kind outside 0..1, n < 0, a keyframe outside [0, kf_cap), kf0 == kf1,
+ * kf0 without a pose (gfpl_mapgeo_set_keyframe), first_new outside [0, lm cap], a NULL or not 8-byte
+ * aligned array of the kind that is read, n above either view's rows or the caps' rows, a pair row
+ * outside its view, an lm_out value outside [-1, lm cap), a created id whose n_obs is not 0 or that two
+ * pairs name, a carried id whose n_obs is 0.  GFPL_E_CAPACITY: a list beyond obs_cap.              */
+int  gfpl_mapgeo_observe_pairs(gfpl_mapgeo* g, int kind, int kf0, int kf1, const gfpl_kf_view* v0, const gfpl_kf_view* v1,
+                               const int32_t* pairs /*DEVICE [n][2]*/, const int32_t* lm_out /*DEVICE [n]*/, int n, int first_new);
+/* The local-map stage (:609-615, :745-764): landmark lm_out[i] receives pl / le of kf1's row
+ * unm_rows[pairs[i][1]] and 1.0; place rule and refusals as above (pairs[i][1] outside [0, n_unm) or a
+ * row outside v1 is GFPL_E_INVALID; column 0 of pairs is not read).                                */
+int  gfpl_mapgeo_observe_local(gfpl_mapgeo* g, int kind, int kf1, const gfpl_kf_view* v1, const int32_t* pairs /*DEVICE [n][2]*/,
+                               int n, const int32_t* unm_rows /*DEVICE [n_unm]*/, int n_unm, const int32_t* lm_out /*DEVICE [n]*/);
+/* n_obs = 0 of the landmarks gfpl_kfmap_remove_bad listed (ledger MG3: no single observation is ever
+ * erased).  GFPL_E_INVALID for an id outside [0, lm cap) or n outside [0, lm cap].                  */
+int  gfpl_mapgeo_free(gfpl_mapgeo* g, int kind, const int32_t* ids /*DEVICE [n]*/, int n);
+/* Read and patch, HOST arrays, ids [id0, id0 + n) below the cap: lm3d [n][3 or 6], n_obs [n], obs
+ * [n][obs_cap][2 or 3], sigma [n][obs_cap].  Reads: any output may be NULL.  Writes take every array;
+ * GFPL_E_INVALID for an n_obs outside [0, obs_cap].                                                */
+int  gfpl_mapgeo_read_landmarks(gfpl_mapgeo* g, int kind, int id0, int n, double* lm3d, int32_t* n_obs, double* obs, double* sigma);
+int  gfpl_mapgeo_write_landmarks(gfpl_mapgeo* g, int kind, int id0, int n, const double* lm3d, const int32_t* n_obs,
+                                 const double* obs, const double* sigma);
+/* HOST copies of an assembled problem's four index lists, each with room for cap_* entries.        */
+typedef struct gfpl_mapgeo_lists {
+    int32_t *pt_obs_lm, *pt_obs_kf;   /* [cap_pt_obs] */
+    int32_t *ls_obs_lm, *ls_obs_kf;   /* [cap_ls_obs] */
+    int32_t cap_pt_obs, cap_ls_obs;
+} gfpl_mapgeo_lists;
+/* The three gathering loops of localBundleAdjustment (:1113-1209, which = GFPL_KFMAP_LOCAL) or
+ * globalBundleAdjustment (:1851-1939, GFPL_KFMAP_ALIVE) on the device, into the object's own buffers;
+ * *problem's double arrays point at them (valid until the next assemble / lba call).  The keyframe
+ * list is alive && local && kf_idx != 0 ascending (ALIVE: every alive keyframe but 0); landmarks in map
+ * order, their observations in list order.  An observation's slot is its keyframe's position in the
+ * list, else -1 - (its position among the fixed keyframes): the alive keyframes outside the list that a
+ * selected landmark's kf_obs names, in ascending index (MG4).  An observation of an erased keyframe is
+ * dropped and a landmark left with none is left out (:1981; for the LBA ledger MG5).  kfmap must have
+ * the object's caps and context.  GFPL_E_INVALID also when a selected landmark's n_obs differs between
+ * the two objects.  With lists, the four index lists are copied to the host in a second
+ * synchronisation and *problem names them, so gfpl_lba_solve / gfpl_gba_check / gfpl_gba_solve take
+ * *problem as it is; GFPL_E_CAPACITY when a list does not fit (problem->n is still set).  Without
+ * lists the problem's index pointers are NULL.  Only workspace is written.                         */
+int  gfpl_mapgeo_assemble(gfpl_mapgeo* g, const gfpl_kfmap* kfmap, int which, gfpl_lba_problem* problem,
+                          const gfpl_mapgeo_lists* lists);
+/* The DEVICE lists of the last assembly's selected ids, for a scatter of a solver's results: kf_list
+ * [n_kf], fix_list [n_fix], pt_list [n_pt], ls_list [n_ls] (any may be NULL).  No synchronisation.  */
+int  gfpl_mapgeo_assembled_ids(gfpl_mapgeo* g, const int32_t** kf_list, const int32_t** fix_list, const int32_t** pt_list,
+                               const int32_t** ls_list);
+/* Read hook: the last assembly's arrays to the HOST.  host's nine double pointers (x_kf ... ls_sigma) name
+ * HOST arrays of the last assembly's counts to fill; its other fields are not read.  host and every
+ * list may be NULL.  After gfpl_mapgeo_lba the doubles are the solver's outputs.                   */
+int  gfpl_mapgeo_read_assembled(gfpl_mapgeo* g, const gfpl_lba_problem* host, int32_t* kf_list, int32_t* fix_list,
+                                int32_t* pt_list, int32_t* ls_list);
+/* The whole of localBundleAdjustment: assemble GFPL_KFMAP_LOCAL, solve on lba (the assembled index
+ * lists reach the solver's workspace on the device), write T_kf_w of the listed keyframes and point3D /
+ * line3D of the listed landmarks back (:1688-1712; x_kf_w is not refreshed, BA1).  Two
+ * synchronisations (counts, result).  No observation: nothing is solved, GFPL_OK, *result zero
+ * (:1212).  GFPL_E_CAPACITY for more than GFPL_LBA_MAX_KFS local keyframes or counts above lba's caps,
+ * GFPL_E_INVALID for observations without a local keyframe (MG6), lba of another context; nothing is
+ * written then.  counts (may be NULL) receives the assembled counts whenever the assembly ran.     */
+int  gfpl_mapgeo_lba(gfpl_mapgeo* g, const gfpl_kfmap* kfmap, gfpl_lba* lba, const gfpl_lba_params* prm,
+                     gfpl_lba_result* result, gfpl_lba_counts* counts);
+/* Instrumentation (tools/bench_mapgeo.py): device milliseconds between the first and the last kernel
+ * of the object's last observe / free / assemble call (for gfpl_mapgeo_lba: its assembly);
+ * GFPL_E_STATE when there is none.                                                                */
+int  gfpl_mapgeo_debug_ms(gfpl_mapgeo* g, float* ms);
+
 /* ------------------------------------------- loop-closure pose graph ----- */
 /* MapHandler::loopClosureOptimizationCovGraphG2O / EssGraphG2O (src/mapHandler.cpp:4187-4419,
  * :3950-4184) for n problems in one call: the pose graph over the keyframes, its
