@@ -242,6 +242,30 @@ hipError_t launch_lm_apply(const LmStoreDev& st, const LmWork* work, const LmOpD
                            int bucket, hipStream_t s);
 hipError_t launch_lm_gather(const LmStoreDev& st, const int32_t* ids, int n, uint8_t* desc_out, int32_t* med_idx_out,
                             hipStream_t s);
+// the same two for a device-planned call: the bucket's range is read from hdr (LM_H_BUCKET) and nothing runs
+// when hdr's error word is set.  n_max: the most work items the bucket can hold (the grid is sized from it)
+hipError_t launch_lm_apply_dev(const LmStoreDev& st, const LmWork* work, const LmOpDev* ops, const int32_t* hdr, int n_max,
+                               int bucket, hipStream_t s);
+hipError_t launch_lm_gather_dev(const LmStoreDev& st, const int32_t* hdr, const int32_t* ids, int n, uint8_t* desc_out,
+                                int32_t* med_idx_out, hipStream_t s);
+// the device planner (k_lm_plan.hip); all pointers device.  The scratch is LmPlanMem's.
+struct LmPlanDev {
+    int32_t *hdr, *pend, *op0, *place, *tile_w, *tile_o;
+    int lm_cap, max_ops, min_g;
+};
+// one observe call.  first_new: ids from here on are created (lm_cap: none, the local-map stage); unm_rows
+// null: column 1 of pairs is a row of desc1, otherwise a row of unm_rows and column 0 is not read
+struct LmObserve {
+    const uint8_t *desc0, *desc1;
+    const int32_t *pairs, *unm_rows, *lm_out;
+    int n, n0, n1, n_unm, first_new;
+};
+// every launch of one call in stream order: check, plan (reduce, scan, scatter, ops), the six buckets
+hipError_t enqueue_lm_observe(const LmStoreDev& st, const LmPlanDev& p, const LmObserve& a, LmWork* work, LmOpDev* ops,
+                              hipStream_t s);
+hipError_t enqueue_lm_free_ids(const LmStoreDev& st, const LmPlanDev& p, const int32_t* ids, int n, hipStream_t s);
+hipError_t enqueue_lm_gather_ids(const LmStoreDev& st, const LmPlanDev& p, const int32_t* ids, int n, uint8_t* desc_out,
+                                 int32_t* med_idx_out, hipStream_t s);
 
 // the loop-closure pose graph (k_pgo.hip): one problem; all pointers device.  The index arrays are
 // PgoIdx's uploaded copies of the planner's lists, m the problem's workspace (PgoMem).

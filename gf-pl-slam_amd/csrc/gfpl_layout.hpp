@@ -354,6 +354,37 @@ struct LmWorkMem {
     size_t bytes = (c.off + 255) & ~(size_t)255;
     LmWorkMem(char* base, int max_ops) : c{0, base}, max_ops(max_ops) {}
 };
+// lanes of bucket b, and the bucket of a list that reaches `peak` observations (at least min_g lanes):
+// the host planner's and the device planner's one rule
+GFPL_HD constexpr int lm_bucket_lanes(int b) { return 2 << b; }
+GFPL_HD inline int lm_bucket_of(int peak, int min_g) {
+    int b = 0;
+    while (b < LM_BUCKETS - 1 && (lm_bucket_lanes(b) < peak || lm_bucket_lanes(b) < min_g)) ++b;
+    return b;
+}
+// the device planner's scratch (k_lm_plan.hip), allocated at a store's first device-id call.  hdr: the
+// call's error word (KFMAP_ERR_* bits), its op count and bucket_start[LM_BUCKETS + 1], zeroed when a
+// call starts and copied to the host once per call.  pend: pairs a landmark receives within the running
+// call (all 0 between calls); op0: a touched landmark's first op.  place: per pair its rank among its
+// landmark's pairs, in pair order.  tile_w / tile_o: work items and ops of every (bucket, tile of
+// LM_PLAN_TILE pairs), bucket-major, then their exclusive scans in place.
+constexpr int LM_PLAN_TILE = 2048;   // pairs per workgroup of the planner's compaction; a thread takes TILE / LM_BLOCK consecutive pairs
+constexpr int LM_HDR = 16;           // int32 words of the header
+enum { LM_H_ERR = 0, LM_H_NOPS, LM_H_BUCKET };   // hdr[LM_H_BUCKET + b] = bucket_start[b], b = 0 .. LM_BUCKETS
+static_assert(LM_H_BUCKET + LM_BUCKETS + 1 <= LM_HDR, "the header holds every bucket's start and the total");
+struct LmPlanMem {
+    Carver c;
+    int lm_cap, max_ops;
+    size_t n_tiles = ((size_t)max_ops + LM_PLAN_TILE - 1) / LM_PLAN_TILE;   // a call has at most max_ops pairs
+    int32_t* hdr = c.take<int32_t>(LM_HDR);
+    int32_t* pend = c.take<int32_t>((size_t)lm_cap);
+    int32_t* op0 = c.take<int32_t>((size_t)lm_cap);
+    int32_t* place = c.take<int32_t>((size_t)max_ops);
+    int32_t* tile_w = c.take<int32_t>(LM_BUCKETS * n_tiles + 1);
+    int32_t* tile_o = c.take<int32_t>(LM_BUCKETS * n_tiles + 1);
+    size_t bytes = (c.off + 255) & ~(size_t)255;
+    LmPlanMem(char* base, int lm_cap, int max_ops) : c{0, base}, lm_cap(lm_cap), max_ops(max_ops) {}
+};
 // (k_lm_apply keeps a group's rows and distances in registers: it has no LDS layout)
 
 // ---- the loop-closure pose graph (k_pgo.hip, gfpl_pgo.cpp, gfpl_pgo_plan.cpp).  Vertices are the

@@ -1,7 +1,10 @@
 // gfpl_lm.cpp — host side of the landmark descriptor store (include/gfpl.h): the
 // object that owns the store's device memory and the host mirror of the counts, apply (the planner,
 // one upload of the work items and ops, one launch per lane-group bucket that has work, one
-// synchronisation), fuse (the same with the planner of gfpl_lm_fuse_plan.cpp), gather and read.
+// synchronisation), fuse (the same with the planner of gfpl_lm_fuse_plan.cpp), gather and read; and
+// the device-id calls (observe_pairs, observe_local, free_ids, gather_ids), whose planner and refusals
+// run on the device (k_lm_plan.hip): the argument checks, the call's launches in stream order, one
+// copy of the header and one synchronisation.
 #include "gfpl_host.hpp"
 #include "gfpl_lm_fuse_plan.hpp"
 #include "gfpl_lm_plan.hpp"
@@ -25,6 +28,11 @@ struct gfpl_lmstore {
     bool timed = false;
     int min_g = 0;                 // GFPL_LM_MIN_LANES as it stood when the store was created
     bool failed = false;           // a HIP call failed inside apply: counts and rows are no longer known
+    // the device-id calls (observe_pairs, observe_local, free_ids, gather_ids)
+    char* plan_base = nullptr;     // LmPlanMem, allocated at the first of them
+    size_t plan_bytes = 0;
+    int32_t* h_hdr = nullptr;      // pinned [LM_HDR]: the header's copy
+    bool stale = false;            // the device's count[] has changed since `counts` was last equal to it
 };
 
 namespace {
@@ -32,6 +40,85 @@ namespace {
 LmStoreDev dev_of(const gfpl_lmstore* st) {
     const LmStoreMem m(st->base, st->lm_cap, st->obs_cap);
     return LmStoreDev{m.rows, m.count, m.med_idx, m.med, st->obs_cap};
+}
+
+LmPlanDev plan_of(const gfpl_lmstore* st) {
+    const LmPlanMem m(st->plan_base, st->lm_cap, st->max_ops);
+    return LmPlanDev{m.hdr, m.pend, m.op0, m.place, m.tile_w, m.tile_o, st->lm_cap, st->max_ops, st->min_g};
+}
+
+bool rows_ok(const uint8_t* p) { return p && ((uintptr_t)p & 15) == 0; }
+
+// The mirror follows the device: a device-id call changes count[] without the host seeing it, so the
+// host-route calls, whose checks run against the mirror, first bring it up to date (one copy of
+// count[lm_cap]; nothing when no device-id call came in between).  DESIGN.md §4i.
+int mirror_refresh(gfpl_lmstore* st) {
+    if (!st->stale) return GFPL_OK;
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(st->ctx)));
+    hipStream_t s = stream_of(st->ctx);
+    const hipError_t e = hipMemcpyAsync(st->counts.data(), dev_of(st).count, (size_t)st->lm_cap * sizeof(int32_t),
+                                        hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e != hipSuccess || es != hipSuccess) {
+        (void)hipGetLastError();
+        return GFPL_E_HIP;   // still stale: the next call tries again
+    }
+    st->stale = false;
+    return GFPL_OK;
+}
+
+// a device-id call's start: the planner's scratch at the first one (pend all zero), the header zeroed,
+// the first event
+int dev_begin(gfpl_lmstore* st, hipStream_t* s) {
+    GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(st->ctx)));
+    *s = stream_of(st->ctx);
+    st->timed = false;
+    if (!st->plan_base) {
+        const size_t bytes = LmPlanMem(nullptr, st->lm_cap, st->max_ops).bytes;
+        char* base = nullptr;
+        int32_t* h = nullptr;
+        if (hipMalloc(&base, bytes) != hipSuccess || hipHostMalloc((void**)&h, LM_HDR * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            if (base) (void)hipFree(base);
+            return GFPL_E_NOMEM;
+        }
+        if (hipMemsetAsync(base, 0, bytes, *s) != hipSuccess || hipStreamSynchronize(*s) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipHostFree(h);
+            (void)hipFree(base);
+            return GFPL_E_HIP;
+        }
+        st->plan_base = base;
+        st->plan_bytes = bytes;
+        st->h_hdr = h;
+    }
+    hipError_t e = hipMemsetAsync(plan_of(st).hdr, 0, LM_HDR * sizeof(int32_t), *s);
+    if (e == hipSuccess) e = hipEventRecord(st->ev0, *s);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return GFPL_E_HIP;   // nothing of the call was enqueued
+    }
+    return GFPL_OK;
+}
+
+// a device-id call's end: the second event, the header to the host, the call's one synchronisation.
+// Returns the call's code: the device's refusal when there is one, GFPL_E_INVALID before GFPL_E_CAPACITY.
+int dev_finish(gfpl_lmstore* st, hipStream_t s, hipError_t e, bool mutates, const char* what) {
+    if (e == hipSuccess) e = hipEventRecord(st->ev1, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(st->h_hdr, plan_of(st).hdr, LM_HDR * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e != hipSuccess || es != hipSuccess) {
+        std::fprintf(stderr, "gfpl: lmstore_%s failed: %s\n", what, hipGetErrorString(e != hipSuccess ? e : es));
+        (void)hipGetLastError();
+        if (mutates) st->failed = true;   // some launches may have run: neither the rows nor the scratch are known
+        return GFPL_E_HIP;
+    }
+    st->timed = true;
+    const int err = st->h_hdr[LM_H_ERR];
+    if (err & KFMAP_ERR_INVALID) return GFPL_E_INVALID;
+    if (err & KFMAP_ERR_CAPACITY) return GFPL_E_CAPACITY;
+    if (mutates) st->stale = true;
+    return GFPL_OK;
 }
 
 }  // namespace
@@ -94,6 +181,8 @@ int gfpl_lmstore_destroy(gfpl_lmstore* st) {
     (void)hipStreamSynchronize(stream_of(st->ctx));
     if (st->h_ids) (void)hipHostFree(st->h_ids);
     if (st->d_ids) (void)hipFree(st->d_ids);
+    if (st->h_hdr) (void)hipHostFree(st->h_hdr);
+    if (st->plan_base) (void)hipFree(st->plan_base);
     (void)hipEventDestroy(st->ev0);
     (void)hipEventDestroy(st->ev1);
     (void)hipHostFree(st->stage);
@@ -104,7 +193,7 @@ int gfpl_lmstore_destroy(gfpl_lmstore* st) {
 }
 
 int64_t gfpl_lmstore_bytes(const gfpl_lmstore* st) {
-    return st ? (int64_t)(st->store_bytes + st->work_bytes + (size_t)st->ids_cap * sizeof(int32_t)) : 0;
+    return st ? (int64_t)(st->store_bytes + st->work_bytes + st->plan_bytes + (size_t)st->ids_cap * sizeof(int32_t)) : 0;
 }
 
 int gfpl_lmstore_apply(gfpl_lmstore* st, const gfpl_lm_op* ops, int n, const uint8_t* const* srcs,
@@ -113,6 +202,7 @@ int gfpl_lmstore_apply(gfpl_lmstore* st, const gfpl_lm_op* ops, int n, const uin
     if (st->failed) return GFPL_E_STATE;
     if (n > st->max_ops) return GFPL_E_CAPACITY;
     if (n == 0) return GFPL_OK;
+    if (const int rm = mirror_refresh(st)) return rm;
     const int rc = lm_plan(ops, n, st->counts.data(), st->lm_cap, st->obs_cap, src_rows, n_srcs, st->min_g, &st->plan,
                            st->slot.data());
     if (rc != GFPL_OK) return rc;
@@ -169,6 +259,7 @@ int gfpl_lmstore_fuse(gfpl_lmstore* st, const gfpl_lm_op* ops, int n, const uint
     if (!st || n < 0 || (n > 0 && !ops) || n_srcs < 0 || (n_srcs > 0 && (!srcs || !src_rows))) return GFPL_E_INVALID;
     if (st->failed) return GFPL_E_STATE;
     if (n == 0) return GFPL_OK;
+    if (const int rm = mirror_refresh(st)) return rm;
     int64_t n_rows = 0;
     LmFusePlan& pl = st->fuse_plan;
     const int rc = lm_fuse_plan(ops, n, st->counts.data(), st->lm_cap, st->obs_cap, src_rows, n_srcs, st->min_g, &n_rows,
@@ -231,6 +322,7 @@ int gfpl_lmstore_gather(gfpl_lmstore* st, const int32_t* lm_ids, int n, uint8_t*
     if (st->failed) return GFPL_E_STATE;
     if (n == 0) return GFPL_OK;
     if ((uintptr_t)desc_out & 15) return GFPL_E_INVALID;
+    if (const int rm = mirror_refresh(st)) return rm;
     for (int i = 0; i < n; ++i)
         if (lm_ids[i] < 0 || lm_ids[i] >= st->lm_cap || st->counts[(size_t)lm_ids[i]] == 0) return GFPL_E_INVALID;
     GFPL_HIPCHK(hipSetDevice(gfpl_ctx_device(st->ctx)));
@@ -263,6 +355,63 @@ int gfpl_lmstore_gather(gfpl_lmstore* st, const int32_t* lm_ids, int n, uint8_t*
         std::fprintf(stderr, "gfpl: lmstore_gather failed: %s\n", hipGetErrorString(e != hipSuccess ? e : es));
         return GFPL_E_HIP;
     }
+    return GFPL_OK;
+}
+
+int gfpl_lmstore_observe_pairs(gfpl_lmstore* st, const uint8_t* desc0, int n0, const uint8_t* desc1, int n1, const int32_t* pairs,
+                               const int32_t* lm_out, int n, int first_new) {
+    if (!st || n < 0 || n0 < 0 || n1 < 0 || (n > 0 && (!desc0 || !desc1 || !pairs || !lm_out))) return GFPL_E_INVALID;
+    if (st->failed) return GFPL_E_STATE;
+    if (first_new < 0 || first_new > st->lm_cap) return GFPL_E_INVALID;
+    if (n == 0) return GFPL_OK;
+    if (!rows_ok(desc0) || !rows_ok(desc1)) return GFPL_E_INVALID;
+    if (n > st->max_ops) return GFPL_E_CAPACITY;
+    hipStream_t s;
+    if (const int rc = dev_begin(st, &s)) return rc;
+    const LmWorkMem dm(st->base + st->store_bytes, st->max_ops);
+    const LmObserve a{desc0, desc1, pairs, nullptr, lm_out, n, n0, n1, 0, first_new};
+    return dev_finish(st, s, enqueue_lm_observe(dev_of(st), plan_of(st), a, dm.work, dm.ops, s), true, "observe_pairs");
+}
+
+int gfpl_lmstore_observe_local(gfpl_lmstore* st, const uint8_t* desc1, int n1, const int32_t* pairs, int n, const int32_t* unm_rows,
+                               int n_unm, const int32_t* lm_out) {
+    if (!st || n < 0 || n1 < 0 || n_unm < 0 || (n > 0 && (!desc1 || !pairs || !unm_rows || !lm_out))) return GFPL_E_INVALID;
+    if (st->failed) return GFPL_E_STATE;
+    if (n == 0) return GFPL_OK;
+    if (!rows_ok(desc1)) return GFPL_E_INVALID;
+    if (n > st->max_ops) return GFPL_E_CAPACITY;
+    hipStream_t s;
+    if (const int rc = dev_begin(st, &s)) return rc;
+    const LmWorkMem dm(st->base + st->store_bytes, st->max_ops);
+    const LmObserve a{nullptr, desc1, pairs, unm_rows, lm_out, n, 0, n1, n_unm, st->lm_cap};   // no id is a created one
+    return dev_finish(st, s, enqueue_lm_observe(dev_of(st), plan_of(st), a, dm.work, dm.ops, s), true, "observe_local");
+}
+
+int gfpl_lmstore_free_ids(gfpl_lmstore* st, const int32_t* ids, int n) {
+    if (!st || n < 0 || (n > 0 && !ids)) return GFPL_E_INVALID;
+    if (st->failed) return GFPL_E_STATE;
+    if (n == 0) return GFPL_OK;
+    hipStream_t s;
+    if (const int rc = dev_begin(st, &s)) return rc;
+    return dev_finish(st, s, enqueue_lm_free_ids(dev_of(st), plan_of(st), ids, n, s), true, "free_ids");
+}
+
+int gfpl_lmstore_gather_ids(gfpl_lmstore* st, const int32_t* ids, int n, uint8_t* desc_out, int32_t* med_idx_out) {
+    if (!st || n < 0 || (n > 0 && (!ids || !desc_out))) return GFPL_E_INVALID;
+    if (st->failed) return GFPL_E_STATE;
+    if (n == 0) return GFPL_OK;
+    if (!rows_ok(desc_out)) return GFPL_E_INVALID;
+    hipStream_t s;
+    if (const int rc = dev_begin(st, &s)) return rc;
+    return dev_finish(st, s, enqueue_lm_gather_ids(dev_of(st), plan_of(st), ids, n, desc_out, med_idx_out, s), false, "gather_ids");
+}
+
+int gfpl_lmstore_counts(gfpl_lmstore* st, int32_t* counts) {
+    if (!st || !counts) return GFPL_E_INVALID;
+    if (st->failed) return GFPL_E_STATE;
+    st->stale = true;   // read from the device whatever the mirror holds, and the mirror with it
+    if (const int rm = mirror_refresh(st)) return rm;
+    std::memcpy(counts, st->counts.data(), (size_t)st->lm_cap * sizeof(int32_t));
     return GFPL_OK;
 }
 

@@ -17,13 +17,7 @@ struct LmPlan {
     int bucket_start[LM_BUCKETS + 1] = {};   // work items of bucket b: [bucket_start[b], bucket_start[b + 1])
 };
 
-// lanes of bucket b, and the bucket of a list that reaches `peak` observations (at least min_g lanes)
-constexpr int lm_bucket_lanes(int b) { return 2 << b; }
-inline int lm_bucket_of(int peak, int min_g) {
-    int b = 0;
-    while (b < LM_BUCKETS - 1 && (lm_bucket_lanes(b) < peak || lm_bucket_lanes(b) < min_g)) ++b;
-    return b;
-}
+// (lm_bucket_lanes / lm_bucket_of: gfpl_layout.hpp, shared with the device planner)
 
 // Checks the ops in array order against counts [lm_cap] (the first op that fails decides the code)
 // and, when all pass, leaves the final counts there; a refused list leaves counts as they were.

@@ -6,6 +6,8 @@
 //                  carries 64 / G landmarks.  The planner (gfpl_lm_plan.cpp) put every touched
 //                  landmark into the launch whose G covers the longest list it reaches.
 //  k_lm_gather   : the median rows of an id list, compacted, 16 bytes per lane.
+//  k_lm_apply<G, LmRangeHdr>, k_lm_gather_dev : the same bodies for a call planned on the device
+//                  (k_lm_plan.hip): the range and the refusal are read from the planner's header.
 // The groups of a wave run different op counts and list lengths: every loop runs to the wave's
 // largest bound (a scalar), so the cross-lane reads stay under uniform control flow, and a group
 // that is done is predicated off.  Rows and distances live in registers with static indices only:
@@ -32,9 +34,31 @@ GFPL_DEV void lm_store_row(uint8_t* p, const uint32_t (&d)[8]) {
     reinterpret_cast<uint4*>(p)[1] = make_uint4(d[4], d[5], d[6], d[7]);
 }
 
-template <int G>
-__global__ void __launch_bounds__(LM_BLOCK) k_lm_apply(LmStoreDev st, const LmWork* work, const LmOpDev* ops, int work0,
-                                                       int n_work) {
+// where a launch's range of work items comes from: the arguments (apply and fuse, planned on the host), or
+// the header a device-planned call's scan left, whose error word also calls the launch off.  That grid is
+// sized on the host from the call's pairs: a workgroup past the bucket's end leaves at once.
+struct LmRangeArgs {
+    int work0, n_work;
+    GFPL_DEV bool get(int, int* w0, int* n) const {
+        *w0 = work0;
+        *n = n_work;
+        return true;
+    }
+};
+struct LmRangeHdr {
+    const int32_t* hdr;
+    int bucket;
+    GFPL_DEV bool get(int per_block, int* w0, int* n) const {
+        *w0 = hdr[LM_H_BUCKET + bucket];
+        *n = hdr[LM_H_BUCKET + bucket + 1] - *w0;
+        return hdr[LM_H_ERR] == 0 && (size_t)blockIdx.x * per_block < (size_t)*n;
+    }
+};
+
+template <int G, typename Range>
+__global__ void __launch_bounds__(LM_BLOCK) k_lm_apply(LmStoreDev st, const LmWork* work, const LmOpDev* ops, Range range) {
+    int work0, n_work;
+    if (!range.get(LM_BLOCK / G, &work0, &n_work)) return;
     const int r = threadIdx.x & (G - 1);
     const size_t wi = ((size_t)blockIdx.x * LM_BLOCK + threadIdx.x) / G;
     const bool live = wi < (size_t)n_work;
@@ -130,8 +154,7 @@ __global__ void __launch_bounds__(LM_BLOCK) k_lm_apply(LmStoreDev st, const LmWo
     }
 }
 
-__global__ void __launch_bounds__(LM_BLOCK) k_lm_gather(LmStoreDev st, const int32_t* ids, int n, uint4* out,
-                                                        int32_t* med_idx_out) {
+GFPL_DEV void lm_gather_rows(const LmStoreDev& st, const int32_t* ids, int n, uint4* out, int32_t* med_idx_out) {
     const size_t t = (size_t)blockIdx.x * LM_BLOCK + threadIdx.x;
     const size_t i = t >> 1;
     if (i >= (size_t)n) return;
@@ -140,12 +163,24 @@ __global__ void __launch_bounds__(LM_BLOCK) k_lm_gather(LmStoreDev st, const int
     if (med_idx_out && !(t & 1)) med_idx_out[i] = st.med_idx[id];
 }
 
+__global__ void __launch_bounds__(LM_BLOCK) k_lm_gather(LmStoreDev st, const int32_t* ids, int n, uint4* out,
+                                                        int32_t* med_idx_out) {
+    lm_gather_rows(st, ids, n, out, med_idx_out);
+}
+
+// the ids were checked on the device (k_lm_ids_check): nothing is written when one was refused
+__global__ void __launch_bounds__(LM_BLOCK) k_lm_gather_dev(LmStoreDev st, const int32_t* hdr, const int32_t* ids, int n, uint4* out,
+                                                            int32_t* med_idx_out) {
+    if (hdr[LM_H_ERR] != 0) return;
+    lm_gather_rows(st, ids, n, out, med_idx_out);
+}
+
 template <int G>
 static hipError_t launch_lm_apply_g(const LmStoreDev& st, const LmWork* work, const LmOpDev* ops, int work0, int n_work,
                                     hipStream_t s) {
     const int per_block = LM_BLOCK / G;
     const unsigned blocks = (unsigned)(((size_t)n_work + per_block - 1) / per_block);
-    hipLaunchKernelGGL(k_lm_apply<G>, dim3(blocks), dim3(LM_BLOCK), 0, s, st, work, ops, work0, n_work);
+    hipLaunchKernelGGL((k_lm_apply<G, LmRangeArgs>), dim3(blocks), dim3(LM_BLOCK), 0, s, st, work, ops, LmRangeArgs{work0, n_work});
     return hipGetLastError();
 }
 
@@ -161,6 +196,38 @@ hipError_t launch_lm_apply(const LmStoreDev& st, const LmWork* work, const LmOpD
     case 5: return launch_lm_apply_g<64>(st, work, ops, work0, n_work, s);
     }
     return hipErrorInvalidValue;
+}
+
+template <int G>
+static hipError_t launch_lm_apply_dev_g(const LmStoreDev& st, const LmWork* work, const LmOpDev* ops, const int32_t* hdr, int n_max,
+                                        int bucket, hipStream_t s) {
+    const int per_block = LM_BLOCK / G;
+    const unsigned blocks = (unsigned)(((size_t)n_max + per_block - 1) / per_block);
+    hipLaunchKernelGGL((k_lm_apply<G, LmRangeHdr>), dim3(blocks), dim3(LM_BLOCK), 0, s, st, work, ops, LmRangeHdr{hdr, bucket});
+    return hipGetLastError();
+}
+
+hipError_t launch_lm_apply_dev(const LmStoreDev& st, const LmWork* work, const LmOpDev* ops, const int32_t* hdr, int n_max,
+                               int bucket, hipStream_t s) {
+    if (n_max <= 0) return hipSuccess;
+    switch (bucket) {
+    case 0: return launch_lm_apply_dev_g<2>(st, work, ops, hdr, n_max, bucket, s);
+    case 1: return launch_lm_apply_dev_g<4>(st, work, ops, hdr, n_max, bucket, s);
+    case 2: return launch_lm_apply_dev_g<8>(st, work, ops, hdr, n_max, bucket, s);
+    case 3: return launch_lm_apply_dev_g<16>(st, work, ops, hdr, n_max, bucket, s);
+    case 4: return launch_lm_apply_dev_g<32>(st, work, ops, hdr, n_max, bucket, s);
+    case 5: return launch_lm_apply_dev_g<64>(st, work, ops, hdr, n_max, bucket, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_lm_gather_dev(const LmStoreDev& st, const int32_t* hdr, const int32_t* ids, int n, uint8_t* desc_out,
+                                int32_t* med_idx_out, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((2 * (size_t)n + LM_BLOCK - 1) / LM_BLOCK);
+    hipLaunchKernelGGL(k_lm_gather_dev, dim3(blocks), dim3(LM_BLOCK), 0, s, st, hdr, ids, n, reinterpret_cast<uint4*>(desc_out),
+                       med_idx_out);
+    return hipGetLastError();
 }
 
 hipError_t launch_lm_gather(const LmStoreDev& st, const int32_t* ids, int n, uint8_t* desc_out, int32_t* med_idx_out,

@@ -718,6 +718,11 @@ def hiplib() -> C.CDLL:
             "gfpl_lmstore_gather": ([P, P, C.c_int, P, P], C.c_int),
             "gfpl_lmstore_read": ([P, C.c_int, P, P, P, P], C.c_int),
             "gfpl_lmstore_debug_ms": ([P, P], C.c_int),
+            "gfpl_lmstore_observe_pairs": ([P, P, C.c_int, P, C.c_int, P, P, C.c_int, C.c_int], C.c_int),
+            "gfpl_lmstore_observe_local": ([P, P, C.c_int, P, C.c_int, P, C.c_int, P], C.c_int),
+            "gfpl_lmstore_free_ids": ([P, P, C.c_int], C.c_int),
+            "gfpl_lmstore_gather_ids": ([P, P, C.c_int, P, P], C.c_int),
+            "gfpl_lmstore_counts": ([P, P], C.c_int),
             "gfpl_default_kfmap_params": ([P], None),
             "gfpl_kfmap_bytes": ([P], C.c_int64),
             "gfpl_kfmap_create": ([P, P, C.POINTER(P)], C.c_int),
@@ -1774,6 +1779,7 @@ class PoseGraph:
 LM_MAX_OBS = 64
 LM_ADD, LM_ERASE_OBS, LM_FREE = 0, 1, 2
 LM_APPEND_LM = 3   # fuse / lm_fuse_check only
+LM_BLOCK, LM_PLAN_TILE = 256, 2048   # the device planner: pairs per workgroup of its check, of its compaction
 
 
 def _lm_ops(ops) -> np.ndarray:
@@ -1809,8 +1815,10 @@ class LandmarkStore:
     """gfpl_lmstore: desc_list and med_desc of lm_cap MapPoints or MapLines on the device
     (src/mapFeatures.cpp:28-92).  apply() takes ops [n][4] (lm, kind, arg, src) and the source
     descriptor arrays (torch device tensors [rows][32] uint8); gather() compacts the median rows of
-    an id list into a device tensor; read() copies one landmark to the host.  The context cannot be
-    closed while the store is open."""
+    an id list into a device tensor; read() copies one landmark to the host.  observe_pairs(),
+    observe_local(), free() and gather_ids() are the same from the device arrays a KeyframeMap leaves
+    (the op list is planned on the device); counts() returns the device's counts.  The context cannot
+    be closed while the store is open."""
 
     def __init__(self, ctx: "Context", lm_cap: int, obs_cap: int, max_ops: int):
         self.ctx, self.L = ctx, ctx.L
@@ -1859,6 +1867,85 @@ class LandmarkStore:
         torch.cuda.synchronize()
         check(self.L.gfpl_lmstore_gather(self.h, _ptr(ids), len(ids), _ptr(out), _ptr(idx)), "lmstore_gather")
         return (out[: len(ids)], idx[: len(ids)]) if with_idx else out[: len(ids)]
+
+    # ---- the device-id calls: the arrays are the ones KeyframeMap / MapGeometry take and return.  A list is a
+    # torch int32 device tensor (a host list is uploaded), a descriptor array a torch uint8 device tensor
+    # [rows][32]; either may be given as a raw (device address, rows) tuple instead.
+    def _list(self, a, cols: int = 0):
+        """(address, rows, the tensor that keeps it alive)"""
+        import torch
+        if isinstance(a, tuple):
+            return int(a[0]), int(a[1]), None
+        if not isinstance(a, torch.Tensor):
+            a = np.ascontiguousarray(a, np.int32)
+            a = a.reshape(-1, cols) if cols else a.reshape(-1)
+            a = torch.from_numpy(a.copy()).to(torch.device("cuda", self.ctx.device))
+        return _ptr(a), int(a.shape[0]), a
+
+    @staticmethod
+    def _rows(d):
+        return (int(d[0]), int(d[1])) if isinstance(d, tuple) else (_ptr(d), int(d.shape[0]))
+
+    def observe_pairs_rc(self, desc0, desc1, pairs, lm_out, first_new: int) -> int:
+        """gfpl_lmstore_observe_pairs' return code."""
+        import torch
+        (d0, n0), (d1, n1) = self._rows(desc0), self._rows(desc1)
+        p, n, _kp = self._list(pairs, 2)
+        out, n_out, _ko = self._list(lm_out)
+        if n_out != n:
+            raise ValueError(f"observe_pairs: {n} pairs, {n_out} lm_out entries")
+        torch.cuda.synchronize()
+        return self.L.gfpl_lmstore_observe_pairs(self.h, d0, n0, d1, n1, p, out, n, int(first_new))
+
+    def observe_pairs(self, desc0, desc1, pairs, lm_out, first_new: int) -> None:
+        """The descriptor half of the keyframe-pair stage: pairs / lm_out / first_new as KeyframeMap.observe_pairs
+        took and returned them, desc0 / desc1 the two keyframes' descriptor rows."""
+        check(self.observe_pairs_rc(desc0, desc1, pairs, lm_out, first_new), "lmstore_observe_pairs")
+
+    def observe_local_rc(self, desc1, pairs, unm_rows, lm_out) -> int:
+        import torch
+        d1, n1 = self._rows(desc1)
+        p, n, _kp = self._list(pairs, 2)
+        unm, n_unm, _ku = self._list(unm_rows)
+        out, n_out, _ko = self._list(lm_out)
+        if n_out != n:
+            raise ValueError(f"observe_local: {n} pairs, {n_out} lm_out entries")
+        torch.cuda.synchronize()
+        return self.L.gfpl_lmstore_observe_local(self.h, d1, n1, p, n, unm, n_unm, out)
+
+    def observe_local(self, desc1, pairs, unm_rows, lm_out) -> None:
+        """The local-map stage: landmark lm_out[i] receives row unm_rows[pairs[i][1]] of desc1."""
+        check(self.observe_local_rc(desc1, pairs, unm_rows, lm_out), "lmstore_observe_local")
+
+    def free_rc(self, ids) -> int:
+        import torch
+        t, n, _k = self._list(ids)
+        torch.cuda.synchronize()
+        return self.L.gfpl_lmstore_free_ids(self.h, t, n)
+
+    def free(self, ids) -> None:
+        """GFPL_LM_FREE of every listed id (KeyframeMap.remove_bad's device list)."""
+        check(self.free_rc(ids), "lmstore_free_ids")
+
+    def gather_ids(self, ids, n: Optional[int] = None, with_idx: bool = False):
+        """gather() with the id list on the device (KeyframeMap.select's tensor); n: the first n ids only."""
+        import torch
+        t, rows, _k = self._list(ids)
+        n = rows if n is None else int(n)
+        if not 0 <= n <= rows:
+            raise ValueError(f"gather_ids: n = {n} of {rows} ids")
+        dev = torch.device("cuda", self.ctx.device)
+        out = torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=dev)
+        idx = torch.full((max(n, 1),), -2, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        check(self.L.gfpl_lmstore_gather_ids(self.h, t, n, _ptr(out), _ptr(idx)), "lmstore_gather_ids")
+        return (out[:n], idx[:n]) if with_idx else out[:n]
+
+    def counts(self) -> np.ndarray:
+        """every landmark's count as the device holds it [lm_cap]"""
+        cnt = np.zeros(self.lm_cap, np.int32)
+        check(self.L.gfpl_lmstore_counts(self.h, _ptr(cnt)), "lmstore_counts")
+        return cnt
 
     def read(self, lm: int) -> dict:
         """count, med_idx, desc_list [obs_cap][32] (rows at and past count are whatever the store

@@ -785,8 +785,63 @@ int  gfpl_lmstore_gather(gfpl_lmstore* st, const int32_t* lm_ids /*HOST [n]*/, i
 int  gfpl_lmstore_read(gfpl_lmstore* st, int lm, int32_t* count, int32_t* med_idx,
                        uint8_t* desc_list /*HOST [obs_cap][32] or NULL*/, uint8_t* med_desc /*HOST [32] or NULL*/);
 /* Instrumentation (tools/bench_lm_store.py): device milliseconds between the first and the last
- * kernel of the store's last apply or gather that launched any; GFPL_E_STATE when there is none. */
+ * kernel of the store's last apply or gather that launched any; GFPL_E_STATE when there is none.
+ * The device-id calls below are covered: from their first kernel to their last.                  */
 int  gfpl_lmstore_debug_ms(gfpl_lmstore* st, float* ms);
+
+/* The device-id calls: the store's half of a keyframe tick from the arrays gfpl_kfmap left on the
+ * device, beside gfpl_mapgeo's calls of the same names (k_lm_plan.hip, DESIGN.md §4i "the device
+ * planner", ledger LM8-LM10).  The op list is built, checked, grouped and
+ * bucketed on the device; nothing but the call's error word comes back.
+ *
+ * Refusals are decided on the device: a check kernel raises bits in an error word, every later
+ * kernel of the call reads the word first and neither indexes with the call's data nor changes the
+ * store when it is set.  A refused call changes nothing and leaves the scratch cleared.  When
+ * refusals of both kinds occur in one call the code is GFPL_E_INVALID (gfpl_mapgeo's rule: the
+ * word keeps both bits, INVALID is read first); which pair raised it is not reported.
+ * GFPL_E_INVALID: a NULL pointer, n < 0 or a negative row count; a descriptor array (desc0, desc1,
+ * desc_out) that is not 16-B aligned (host checks); a pair row outside [0, n0) / [0, n1) /
+ * [0, n_unm); an unm_rows value outside [0, n1); an lm_out value outside [-1, lm_cap) or an id
+ * outside [0, lm_cap); first_new outside [0, lm_cap]; a created id (>= first_new) whose list is not
+ * empty or that two pairs name; a carried id whose list is empty; a gathered id whose list is empty.
+ * GFPL_E_CAPACITY: a list that would pass obs_cap; n > max_ops (host check: the scratch holds one
+ * word per pair); a call whose ops, two per created pair and one per carried pair, exceed max_ops
+ * (decided on the device from the call's own op count: max_ops >= 2 n always suffices for
+ * observe_pairs and max_ops >= n for observe_local; free_ids and gather_ids use no ops and take
+ * any n).  GFPL_E_STATE as for apply; GFPL_E_HIP from an observe or free call leaves the contents
+ * unknown as for apply, GFPL_E_NOMEM when the scratch cannot be allocated (at the first of these
+ * calls: a store that never uses them keeps its gfpl_lmstore_bytes).  Each call synchronises
+ * once; n = 0 returns GFPL_OK without a launch.  The arrays are read during the call.
+ *
+ * The device's counts are the authority: these calls change them without the host seeing it, so
+ * the next apply, fuse or host-id gather first refreshes the store's host mirror with one copy of
+ * count[lm_cap] (calls that never mix the two routes pay nothing).                               */
+/* The descriptor half of lookForCommonMatches' keyframe-pair body (src/mapHandler.cpp:280, :287,
+ * :315): pairs, lm_out and first_new are what gfpl_kfmap_observe_pairs took and returned, desc0 /
+ * desc1 kf0's / kf1's pdesc (ldesc) rows.  Pair i in pair order: lm_out[i] == -1 nothing (:308);
+ * lm_out[i] >= first_new (created) ADD row pairs[i][0] of desc0, then ADD row pairs[i][1] of
+ * desc1; otherwise (carried) ADD row pairs[i][1] of desc1.  Several pairs may carry one landmark:
+ * their rows are appended in pair order (gfpl_mapgeo_observe_pairs' "place").  Afterwards every
+ * landmark named has the count / med_idx / med_desc of updateAverageDescDir over its final list. */
+int  gfpl_lmstore_observe_pairs(gfpl_lmstore* st, const uint8_t* desc0 /*DEVICE [n0][32]*/, int n0,
+                                const uint8_t* desc1 /*DEVICE [n1][32]*/, int n1,
+                                const int32_t* pairs /*DEVICE [n][2]*/, const int32_t* lm_out /*DEVICE [n]*/, int n,
+                                int first_new);
+/* The local-map stage (:615, :757): landmark lm_out[i] receives row unm_rows[pairs[i][1]] of desc1;
+ * column 0 of pairs is not read and every named landmark is a carried one.                      */
+int  gfpl_lmstore_observe_local(gfpl_lmstore* st, const uint8_t* desc1 /*DEVICE [n1][32]*/, int n1,
+                                const int32_t* pairs /*DEVICE [n][2]*/, int n,
+                                const int32_t* unm_rows /*DEVICE [n_unm]*/, int n_unm, const int32_t* lm_out /*DEVICE [n]*/);
+/* GFPL_LM_FREE of every listed id (the list gfpl_kfmap_remove_bad wrote): count 0, med_idx -1, a
+ * zeroed median row, the rows as they are.  An empty landmark or a repeated id is allowed.      */
+int  gfpl_lmstore_free_ids(gfpl_lmstore* st, const int32_t* ids /*DEVICE [n]*/, int n);
+/* gfpl_lmstore_gather with the id list on the device (gfpl_kfmap_select's output).  A refused
+ * call writes neither desc_out nor med_idx_out.                                                 */
+int  gfpl_lmstore_gather_ids(gfpl_lmstore* st, const int32_t* ids /*DEVICE [n]*/, int n,
+                             uint8_t* desc_out /*DEVICE [n][32], 16-B aligned*/, int32_t* med_idx_out /*DEVICE [n] or NULL*/);
+/* Every landmark's count as the device holds it (one copy, one synchronisation; the host mirror is
+ * refreshed with it): what a caller of the device-id calls hands gfpl_lm_ops_check.             */
+int  gfpl_lmstore_counts(gfpl_lmstore* st, int32_t* counts /*HOST [lm_cap]*/);
 
 /* Ops that cross landmarks: what MapHandler::loopClosureFuseLandmarks (src/mapHandler.cpp:4425 ff.)
  * does to desc_list, without a descriptor leaving the device (DESIGN.md §4i "fuse").             */
